@@ -20,13 +20,24 @@ starts N rank processes as fresh children before it touches the GPU, relays
 rank 0's JSON line and exits non-zero when any rank fails. Every rank checks
 that the process group has exactly --gpus ranks, each on its own GPU.
 
-Extra JSON fields:
+A plain run sets up, warms up, times the K steps and prints the JSON line:
+metric, value, ms_per_step (wall milliseconds per timed step) and
   roofline      dominant kernel's algorithmic bytes per launch / its average
-                launch duration (HIP events on the launch stream) vs 8 TB/s;
-  cpu_baseline  the reference's own CPU path (oracle/_ref/libisal_ref.so =
-                /root/reference erasure_code/ec_base.c built for this box's
-                host; nasm is absent so the AVX-512/GFNI kernels cannot be
-                assembled) on a bounded sample, rank 0 only.
+                launch duration (HIP events on the launch stream around the K
+                timed steps) vs 8 TB/s.
+--dump-outputs DIR also writes what the last timed step computed (rank 0's
+arrays) as DIR/<name>.npy; the inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
+
+--full adds everything that takes work of its own after the timed steps:
+  self_check, shard_crc32c_digest   extra launches over the resident batch;
+  roofline.traffic / profile_*      looked up in the committed profiles/;
+  roofline.copy_ceiling             a 2 GiB copy kernel timed in this process;
+  cpu_baseline*                     the reference's own CPU path
+                (oracle/_ref/libisal_ref.so, its portable ec_base.c: without
+                nasm the AVX-512/GFNI kernels cannot be assembled) and an
+                AVX-512+GFNI port of its fast path on a bounded sample, rank 0
+                only (--no-cpu-baseline leaves these out of a --full run).
 """
 from __future__ import annotations
 
@@ -52,8 +63,15 @@ def parse_args(argv=None):
                     help="ranks (one per GPU). Without a torchrun environment and N > 1 this script "
                          "starts the N rank processes itself; under torchrun it must equal WORLD_SIZE. "
                          "Default: WORLD_SIZE, else 1")
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=5, help="untimed steps before them")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the self-checks, the shard digest, the copy-kernel "
+                         "ceiling, the look-ups in profiles/ and the CPU baselines (dropin: every thread "
+                         "count; c1: the reference's CPU path beside the engine's)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 or "
+                         "float64, at most 64 MB in all (a fixed seeded sample of larger arrays)")
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--p", type=int, default=4)
     ap.add_argument("--len", type=int, default=1 << 20, help="shard bytes")
@@ -239,6 +257,41 @@ def timed_steps(d: Dist, step, sync, steps: int, warmup: int):
     t1 = time.perf_counter()
     d.barrier()
     return d.max(t1 - t0)
+
+
+DUMP_BUDGET = 64_000_000  # bytes of --dump-outputs files in all
+DUMP_SEED = 20240229  # of the generator that draws a sampled array's indices
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write each of `arrays` (name -> torch tensor, on the GPU
+    or the host) as path/<name>.npy. Bytes become float32; 32-bit checksums
+    their unsigned value in float64; 64-bit words two float64 arrays,
+    <name>_hi32 and <name>_lo32 (a float64 holds 53 bits). Every value is
+    exact. An array over its share of DUMP_BUDGET is sampled: the elements at
+    fixed flat indices drawn once from a seeded host generator, in ascending
+    order, the same for every run with the same shapes."""
+    import numpy as np
+    import torch
+
+    items = []
+    for name, t in arrays.items():
+        if t.dtype == torch.int64:
+            items += [(name + "_hi32", (t >> 32) & 0xFFFFFFFF, np.float64),
+                      (name + "_lo32", t & 0xFFFFFFFF, np.float64)]
+        elif t.dtype == torch.int32:
+            items.append((name, t.to(torch.int64) & 0xFFFFFFFF, np.float64))
+        else:
+            items.append((name, t, np.float32))
+    os.makedirs(path, exist_ok=True)
+    for name, t, ft in items:
+        cap = (DUMP_BUDGET // len(items) - 4096) // np.dtype(ft).itemsize  # 4096: room for the .npy header
+        flat = t.reshape(-1)
+        if flat.numel() > cap:
+            idx = torch.randint(0, flat.numel(), (cap,), generator=torch.Generator().manual_seed(DUMP_SEED))
+            flat = flat[idx.sort().values.to(flat.device)]
+        np.save(os.path.join(path, name + ".npy"), flat.cpu().numpy().astype(ft).reshape(
+            t.shape if flat.numel() == t.numel() else -1))
 
 
 def enc_kernel(rows: int, k: int, coef) -> str:
@@ -811,13 +864,15 @@ def total_stripes_run(args, d: Dist, a, k, p, n):
     d.barrier()
     wall = d.max(t1 - t0)
     step_s = ev0.elapsed_time(ev1) / 1e3 / args.steps
+    if args.dump_outputs and d.rank == 0:
+        dump_outputs(args.dump_outputs, {"parity": out})
 
-    # self-check (all-ones Vandermonde row) and a digest of this rank's shards:
-    # CRC32C of every source and parity shard of the resident batch, summed
+    # --full: self-check (all-ones Vandermonde row) and a digest of this rank's
+    # shards: CRC32C of every source and parity shard of the resident batch, summed
     # (a rank whose range is empty — fewer stripes than ranks — encoded nothing
     # and has nothing to check or digest)
     ok, digest = True, 0
-    if count:
+    if count and args.full:
         for s_ in sorted({0, B // 2, B - 1}):
             x = data[s_, 0].clone()
             for j in range(1, k):
@@ -863,8 +918,9 @@ def total_stripes_run(args, d: Dist, a, k, p, n):
         "per_gpu_gib_s": round(value / W, 2),
         "stripes_encoded": encoded,
         "stripes_expected": T * args.steps,
-        "shard_crc32c_digest": digest_all,
-        "self_check": bad == 0 and encoded == T * args.steps,
+        "full": args.full,
+        "shard_crc32c_digest": digest_all if args.full else None,
+        "self_check": (bad == 0 and encoded == T * args.steps) if args.full else None,
         "self_check_method": "3 stripes per rank: parity row 0 == XOR of the sources, and a decode round trip "
                              "(min(p,k) data shards erased, recovered from the survivors incl. every parity row "
                              "with gf_invert_matrix + the engine, == the originals)",
@@ -972,6 +1028,9 @@ def main(argv=None):
         raise SystemExit("bench.py: --gpus must be >= 1")
     if (args.gpus or 1) > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args, argv)
+    if args.dump_outputs and (args.dry_run or args.workload == "dropin"):
+        # the dry run computes nothing; the drop-in driver is a C program that keeps its buffers
+        raise SystemExit("bench.py: --dump-outputs is not available with --dry-run or --workload dropin")
     if args.workload == "c1":
         return c1_cpu(args)
     if args.workload == "dropin":
@@ -1150,12 +1209,24 @@ def main(argv=None):
     d.barrier()
     wall = d.max(t1 - t0)
     launch_s = ev0.elapsed_time(ev1) / 1e3 / args.steps
+    if args.dump_outputs and d.rank == 0:
+        # what a caller of the timed path receives, before any check touches it
+        if args.workload == "pq_check":
+            dump = {"first_bad": bad}
+        elif args.workload in ("crc", "crc64"):
+            dump = {"crc": crc_out}
+        else:
+            dump = {"recovered" if args.workload == "decode" else "parity": out}
+            if args.workload in ("encode-crc", "encode-crc64"):
+                dump["crc"] = crc_out
+        dump_outputs(args.dump_outputs, dump)
 
-    # Self-check on this rank's own batch (no oracle): Vandermonde parity row 0
-    # is all ones, so it must equal the XOR of the sources; decode must return
-    # exactly the erased shards. Reduced with MIN over ranks.
+    # --full: self-check on this rank's own batch (no oracle): Vandermonde parity
+    # row 0 is all ones, so it must equal the XOR of the sources; decode must
+    # return exactly the erased shards. Reduced with MIN over ranks.
     ok = True
-    if args.workload in ("encode-crc", "crc"):
+    check = args.workload if args.full else None
+    if check in ("encode-crc", "crc"):
         # the fused kernel and the checksum-only kernel must agree on every shard
         crc_ref = torch.zeros_like(crc_out)
         if args.workload == "encode-crc":
@@ -1164,13 +1235,13 @@ def main(argv=None):
             batch.encode_crc(0xFFFFFFFF, crc_ref, h)
         torch.cuda.synchronize(dev)
         ok &= bool(torch.equal(crc_ref, crc_out))
-    if args.workload == "encode-crc64":
+    if check == "encode-crc64":
         # the fused kernel and the standalone CRC64 pass must agree on every shard
         crc_ref = torch.zeros_like(crc_out)
         batch.crc64(0, 0, crc_ref, h)
         torch.cuda.synchronize(dev)
         ok &= bool(torch.equal(crc_ref, crc_out))
-    if args.workload in ("crc64", "encode-crc64"):
+    if check in ("crc64", "encode-crc64"):
         # CRC64 is affine in the data: crc(x) = L(x) ^ crc(0^n). Parity row 0 is
         # the XOR of the k sources, so crc(P0) = XOR_j crc(d_j) ^ ((k+1)&1)*crc(0^n).
         zero = torch.zeros((2, n), dtype=torch.uint8, device=dev)
@@ -1186,7 +1257,7 @@ def main(argv=None):
             for j in range(k):
                 x ^= int(got[s_, j])
             ok &= x == int(got[s_, k])
-    if args.workload in ("encode", "encode-crc", "encode-crc64"):
+    if check in ("encode", "encode-crc", "encode-crc64"):
         for s_ in sorted({0, S // 2, S - 1}):
             x = data[s_, 0].clone()
             for j in range(1, k):
@@ -1195,14 +1266,14 @@ def main(argv=None):
             # every parity row: erase data shards, decode with the engine, compare
             ok &= decode_roundtrip(k, p, n, a, [data[s_, j] for j in range(k)], [out[s_, l] for l in range(p)],
                                    s_ + d.rank * S)
-    elif args.workload == "decode":
+    elif check == "decode":
         for i, e in enumerate(errs):
             ok &= bool(torch.equal(out[:, i], data[:, e]))
-    elif args.workload in RAID_ROWS:
+    elif check in RAID_ROWS:
         ok &= raid_self_check(args.workload, batch, data, out, k, p, n, S, h, dev)
-    self_check = None if args.workload == "update" else bool(d.max(0.0 if ok else 1.0) == 0.0)
+    self_check = None if check in (None, "update") else bool(d.max(0.0 if ok else 1.0) == 0.0)
     digest = None
-    if args.workload in ("encode", "decode"):
+    if check in ("encode", "decode"):
         # control-plane digest of every rank's shards: CRC32C of all sources and
         # parity of the batch, summed on each rank and all-reduced (RCCL)
         dg = torch.zeros(S * (batch.k + batch.rows), dtype=torch.int32, device=dev)
@@ -1244,6 +1315,7 @@ def main(argv=None):
             "parallelism": f"stripes sharded over {d.world} GPU(s), no data-path collective",
         },
         "payload_gib_s": round(k * n * S * args.steps * d.world / wall / GIB, 2),
+        "full": args.full,
         "self_check": self_check,
         "self_check_method": SELF_CHECK_METHOD.get(args.workload),
         "shard_crc32c_digest": digest,
@@ -1260,24 +1332,24 @@ def main(argv=None):
         },
         **d.info(),
     }
-    traffic = pmc_traffic(args.workload, k, p, n, S, kernel)
+    traffic = pmc_traffic(args.workload, k, p, n, S, kernel) if args.full else None
     if traffic:
         result["roofline"]["traffic"] = traffic[0]
         result["roofline"]["traffic_source"] = traffic[1]
-    prof = kernel_stats(args.workload, k, p, n, S, kernel)
+    prof = kernel_stats(args.workload, k, p, n, S, kernel) if args.full else None
     if prof:
         # the committed rocprofv3 steady-state average of the same kernel and
         # configuration (another run, possibly another box): the cross-check
         result["roofline"]["profile_launch_ms"] = round(prof[0], 4)
         result["roofline"]["profile_frac"] = round(bytes_per_launch / (prof[0] / 1e3) / 1e9 / HBM_PEAK_GBS, 4)
         result["roofline"]["kernel_stats_source"] = prof[1]
-    if d.world == 1:
+    if args.full and d.world == 1:
         # the achievable peak, measured live with a device copy
         cc = copy_ceiling(dev)
         result["roofline"]["copy_ceiling"] = cc
         result["roofline"]["frac_of_copy_ceiling"] = round(achieved / cc["gb_s"], 4)
 
-    if d.rank == 0 and d.world == 1 and not args.no_cpu_baseline:
+    if args.full and d.rank == 0 and d.world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(REPO, "tools"))
         import cpu_ref_baseline as crb
 
@@ -1331,7 +1403,8 @@ def c1_cpu(args):
     beside the reference's ec_encode_data_base (oracle/_ref/libisal_ref.so,
     erasure_code/ec_base.c built from /root/reference; the same loop
     erasure_code_base_perf.c times), both single-threaded, and checks that
-    both give the reference fixture's parity (FNV-1a of each row)."""
+    both give the reference fixture's parity (FNV-1a of each row). The
+    reference's side runs only with --full."""
     import numpy as np
 
     import isal_amd
@@ -1362,7 +1435,7 @@ def c1_cpu(args):
     ok_eng = [fnv(x) for x in dst] == case["fnv"]
     ref = None
     path = os.path.join(REPO, "oracle", "_ref", "libisal_ref.so")
-    if os.path.exists(path):
+    if args.full and os.path.exists(path):
         R = ctypes.CDLL(path)
         u8p = ctypes.POINTER(ctypes.c_ubyte)
         rt = np.zeros(32 * k * p, np.uint8)
@@ -1390,9 +1463,14 @@ def c1_cpu(args):
         "config": {"workload": "C1: k=4 p=2 Cauchy RS (gf_gen_cauchy1_matrix), one stripe of 64 KiB shards, "
                                "drop-in ec_encode_data on host buffers (engine CPU route)",
                    "k": k, "p": p, "shard_bytes": n},
+        "full": args.full,
         "parity_matches_fixture": ok_eng,
         "cpu_baseline": ref,
     }
+    if args.dump_outputs:
+        import torch
+
+        dump_outputs(args.dump_outputs, {"parity": torch.from_numpy(np.stack(dst))})
     print(json.dumps(result), flush=True)
     return 0 if ok_eng else 1
 
@@ -1417,7 +1495,8 @@ def dropin(args):
         p = 2 if op.startswith("pq") else 1
     stripes = min(args.stripes, 64)
     runs = []
-    for t in [int(x) for x in args.dropin_threads.split(",") if x]:
+    counts = [int(x) for x in args.dropin_threads.split(",") if x]
+    for t in counts if args.full else counts[-1:]:  # value is the last count's; --full runs them all
         r = subprocess.run([exe, str(k), str(p), str(n), str(stripes), str(t), str(args.dropin_seconds), "0",
                             args.dropin_op],
                            capture_output=True, text=True, timeout=120 + 2 * args.dropin_seconds)
@@ -1446,12 +1525,27 @@ def dropin(args):
                    "k": k, "p": p, "shard_bytes": n},
         "threads": [{a: r[a] for a in ("threads", "calls", "us_per_call", "calls_per_s", "gib_s", "self_check")}
                     for r in runs],
+        "full": args.full,
         "self_check": all(r["self_check"] for r in runs),
         "roofline": None,
         "cpu_baseline": None,
     }
     print(json.dumps(result), flush=True)
     return 0 if result["self_check"] else 1
+
+
+def e2e_spot_check(d: Dist, a, k, p, n, src, par) -> bool:
+    """--full: one host stripe's parity from the pipeline equals a
+    device-resident re-encode of its sources."""
+    import torch
+
+    import isal_amd
+
+    dsrc = src.to(dev := torch.device("cuda", d.gpu))
+    dpar = torch.empty((p, n), dtype=torch.uint8, device=dev)
+    isal_amd.ec_encode_data(n, k, p, isal_amd.ec_init_tables(k, p, a[k * k:]),
+                            [dsrc[j] for j in range(k)], [dpar[l] for l in range(p)])
+    return bool(torch.equal(dpar.cpu(), par))
 
 
 def e2e(args, d: Dist, a, k, p, n):
@@ -1481,13 +1575,9 @@ def e2e(args, d: Dist, a, k, p, n):
 
     wall = timed_steps(d, step, pipe.flush, args.steps, args.warmup)
     total = (k + p) * n * args.steps * d.world
-    # spot check: the last stripe's parity equals a device-resident re-encode
-    r = (i[0] - 1) % ring
-    dsrc = src[r].to(dev := torch.device("cuda", d.gpu))
-    dpar = torch.empty((p, n), dtype=torch.uint8, device=dev)
-    isal_amd.ec_encode_data(n, k, p, isal_amd.ec_init_tables(k, p, a[k * k:]),
-                            [dsrc[j] for j in range(k)], [dpar[l] for l in range(p)])
-    ok = bool(torch.equal(dpar.cpu(), par[r]))
+    if args.dump_outputs and d.rank == 0:
+        dump_outputs(args.dump_outputs, {"parity": par})
+    ok = e2e_spot_check(d, a, k, p, n, src[(i[0] - 1) % ring], par[(i[0] - 1) % ring]) if args.full else None
     result = {
         "metric": f"{args.workload} GiB/s host-resident (pinned) end-to-end incl. H2D/D2H",
         "value": round(total / wall / GIB, 3),
@@ -1507,6 +1597,7 @@ def e2e(args, d: Dist, a, k, p, n):
         "pcie": {"h2d_gb_s": round(k * n * args.steps / wall / 1e9, 2),
                  "d2h_gb_s": round(p * n * args.steps / wall / 1e9, 2),
                  "peak_gb_s_per_direction": 63.0},
+        "full": args.full,
         "parity_check_last_stripe": ok,
         "cpu_baseline": None,
         **d.info(),

@@ -58,6 +58,38 @@ def test_erasure_sets_rotate_and_stay_in_range():
     assert bench.erasure_set(3, 5, 0) == [0, 1, 2]
 
 
+def test_dump_outputs_exact_bounded_and_repeatable(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: bytes as float32, 32-bit checksums as float64,
+    64-bit words as two float64 halves, every value exact; an array over its
+    share of the budget is sampled at the same indices on every run, and the
+    files together stay under the budget."""
+    import torch
+
+    g = torch.Generator().manual_seed(3)
+    small = torch.randint(0, 256, (3, 2, 100), dtype=torch.uint8, generator=g)
+    big = torch.randint(0, 256, (8, 4, 4096 + 3), dtype=torch.uint8, generator=g)
+    crc = torch.randint(-2 ** 31, 2 ** 31 - 1, (113,), dtype=torch.int32, generator=g)
+    c64 = torch.randint(-2 ** 63, 2 ** 63 - 1, (113,), dtype=torch.int64, generator=g)
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 200_000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "parity": big, "crc": crc, "crc64": c64})
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["crc.npy", "crc64_hi32.npy", "crc64_lo32.npy", "parity.npy", "small.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 200_000
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in names}
+    for f in names:
+        assert np.array_equal(got[f[:-4]], np.load(tmp_path / "b" / f)), f
+    assert got["small"].dtype == np.float32 and np.array_equal(got["small"], small.numpy())
+    assert got["crc"].dtype == np.float64 and np.array_equal(got["crc"].astype(np.uint32), crc.numpy().view(np.uint32))
+    words = (got["crc64_hi32"].astype(np.uint64) << np.uint64(32)) | got["crc64_lo32"].astype(np.uint64)
+    assert np.array_equal(words, c64.numpy().view(np.uint64))
+    # the sample: a fifth of the budget (five files), each value one of the array's own, in index order
+    samp = got["parity"]
+    assert samp.dtype == np.float32 and samp.ndim == 1 and 8000 < samp.size < big.numel()
+    idx = torch.randint(0, big.numel(), (samp.size,), generator=torch.Generator().manual_seed(bench.DUMP_SEED))
+    assert np.array_equal(samp, big.reshape(-1)[idx.sort().values].numpy())
+
+
 def test_cpu_baseline_cores_spread_over_l3_domains(monkeypatch):
     """The CPU baseline pins one thread per physical core, round-robin over
     the L3 domains (tools/cpu_ref_baseline.py _physical_cpus): on a host of

@@ -262,7 +262,7 @@ def test_bench_c1_cpu_plumbing():
     import sys
 
     r = subprocess.run([sys.executable, os.path.join(ecutil.REPO, "bench.py"), "--workload", "c1",
-                        "--cpu-seconds", "0.2"], capture_output=True, text=True, timeout=300, cwd=ecutil.REPO)
+                        "--full", "--cpu-seconds", "0.2"], capture_output=True, text=True, timeout=300, cwd=ecutil.REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert out["parity_matches_fixture"] is True and out["value"] > 0

@@ -1740,7 +1740,7 @@ def test_bench_two_ranks_on_one_gpu(gpu):
     # both ranks itself (gloo lets them share this box's one GPU)
     env = {a: b for a, b in os.environ.items() if a not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ecutil.REPO, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
-           "--stripes", "64", "--len", "65536", "--steps", "4", "--warmup", "1"]
+           "--stripes", "64", "--len", "65536", "--steps", "4", "--warmup", "1", "--full"]
     for workload in ("encode", "decode"):
         r = subprocess.run(cmd + ["--workload", workload], capture_output=True, text=True,
                            timeout=600, cwd=ecutil.REPO, env=env)
@@ -1783,7 +1783,7 @@ def test_c5_full_workload_eight_ranks(gpu):
     T, W, steps = 1 << 20, 8, 1
     r = subprocess.run([sys.executable, os.path.join(ecutil.REPO, "bench.py"), "--gpus", str(W),
                         "--dist-backend", "gloo", "--total-stripes", str(T), "--len", str(1 << 20),
-                        "--stripes", "256", "--steps", str(steps), "--warmup", "1"],
+                        "--stripes", "256", "--steps", str(steps), "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ecutil.REPO, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -1868,7 +1868,7 @@ def test_bench_rccl_control_plane_single_rank(gpu):
                "--master-addr", "127.0.0.1", "--master-port", str(port),
                os.path.join(ecutil.REPO, "bench.py"), "--dist-always", "--dist-backend", "nccl",
                "--stripes", "32", "--len", "65536", "--steps", "3", "--warmup", "1",
-               "--no-cpu-baseline"] + extra
+               "--full", "--no-cpu-baseline"] + extra
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ecutil.REPO)
         assert r.returncode == 0, r.stderr[-3000:]
         out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -1914,6 +1914,40 @@ def test_bench_kernel_label_matches_launch(gpu, args, env):
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     launched = {l.split("kernel ", 1)[1] for l in r.stderr.splitlines() if l.startswith("isal_hip: kernel ")}
     assert out["roofline"]["kernel"] in launched, (out["roofline"]["kernel"], launched)
+
+
+def test_bench_plain_run_times_only_and_dumps_its_parity(oracle, gpu, tmp_path):
+    """A plain `bench.py` run: --steps timed steps, `ms_per_step` from them, and
+    nothing that takes work of its own (self-check, digest, copy ceiling, CPU
+    baselines: --full). --dump-outputs writes the parity of the last step, and
+    the inputs are the seeded bytes every run draws: == the oracle's parity of
+    the same bytes."""
+    import json
+    import sys
+    import torch
+
+    k, p, n, S = 10, 4, 65536, 3
+    r = subprocess.run([sys.executable, os.path.join(ecutil.REPO, "bench.py"), "--gpus", "1", "--steps", "3",
+                        "--warmup", "1", "--len", str(n), "--stripes", str(S), "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=300, cwd=ecutil.REPO)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    # value and ms_per_step describe the same steps (ms_per_step is printed to 1e-4 ms: 2 % of a 5 us step)
+    assert abs(out["value"] - (k + p) * n * S / (out["ms_per_step"] / 1e3) / 2 ** 30) <= 0.02 * out["value"]
+    assert out["full"] is False and out["self_check"] is None and out["shard_crc32c_digest"] is None
+    assert out["cpu_baseline"] is None and "copy_ceiling" not in out["roofline"]
+    assert os.listdir(tmp_path) == ["parity.npy"]
+    got = np.load(tmp_path / "parity.npy")
+    assert got.dtype == np.float32 and got.shape == (S, p, n)
+    data = torch.empty((S, k, n), dtype=torch.uint8, device=gpu)
+    data.random_(generator=torch.Generator(device=gpu).manual_seed(1234))  # bench.py's rank 0
+    h = data.cpu().numpy()
+    a = oracle.gf_gen_rs_matrix(k + p, k)
+    for s in range(S):
+        want = oracle.encode(a[k * k:], k, p, [h[s, j] for j in range(k)])
+        for l in range(p):
+            assert np.array_equal(got[s, l], want[l].astype(np.float32)), (s, l)
 
 
 def test_multi_device_encode_host_stripes_vs_oracle(engine, oracle, gpu):

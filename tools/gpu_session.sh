@@ -59,19 +59,19 @@ for s in $STEPS; do
                 ;;
         gpus2)
                 # the driver's N>1 form on this one-GPU box: two gloo ranks share the GPU
-                run bench_gpus2_gloo 300 python bench.py --gpus 2 --dist-backend gloo --no-cpu-baseline
+                run bench_gpus2_gloo 300 python bench.py --full --gpus 2 --dist-backend gloo --no-cpu-baseline
                 ;;
         gpus8)
                 # rehearsal of the driver's N=8 launch forms on this one-GPU box: eight gloo
                 # ranks share the GPU (RCCL needs one GPU per rank), 128 stripes per rank
-                run bench_gpus8_gloo 300 python bench.py --gpus 8 --dist-backend gloo --stripes 128 --no-cpu-baseline
-                run bench_gpus4_torchrun_gloo 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 4 --dist-backend gloo --stripes 128 --no-cpu-baseline
-                run bench_c5_gpus8_gloo 300 python bench.py --gpus 8 --dist-backend gloo --total-stripes 8192 --stripes 128 --steps 2 --warmup 1 --no-cpu-baseline
+                run bench_gpus8_gloo 300 python bench.py --full --gpus 8 --dist-backend gloo --stripes 128 --no-cpu-baseline
+                run bench_gpus4_torchrun_gloo 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 4 --dist-backend gloo --stripes 128 --no-cpu-baseline
+                run bench_c5_gpus8_gloo 300 python bench.py --full --gpus 8 --dist-backend gloo --total-stripes 8192 --stripes 128 --steps 2 --warmup 1 --no-cpu-baseline
                 ;;
         steady)
                 # C2 headline kernel: per-dispatch trace, steady-state average of the
                 # K timed launches (tools/kernel_stats.py), beside the bench line
-                run bench_c2 300 python bench.py --no-cpu-baseline
+                run bench_c2 300 python bench.py --full --no-cpu-baseline
                 cp "$OUT/bench_c2.log" "$OUT/bench_c2.json"
                 run rocprof_c2 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_c2" -o c2 -- python3 bench.py --no-cpu-baseline
                 run steady_c2 60 python3 tools/kernel_stats.py "$OUT/prof_c2" "ec_encode_v16<4" --skip 5 --keep 20 --bytes 15032385536 --out "$OUT/c2_encode_kernel_steady.csv" --config "workload=encode k=10 p=4 len=1048576 stripes=1024" --command "rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline"
@@ -80,7 +80,7 @@ for s in $STEPS; do
                 # the round's headline evidence for one tree: C2 line (with the CPU
                 # baseline), its rocprofv3 trace + steady-state summary, PMC traffic;
                 # C3 decode the same way
-                run bench_c2 300 python bench.py
+                run bench_c2 300 python bench.py --full
                 cp "$OUT/bench_c2.log" "$OUT/bench_c2.json"
                 run rocprof_c2 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_c2" -o c2 -- python3 bench.py --no-cpu-baseline
                 run steady_c2 60 python3 tools/kernel_stats.py "$OUT/prof_c2" "ec_encode_v16<4" --skip 5 --keep 20 --bytes 15032385536 --out "$OUT/c2_encode_kernel_steady.csv" --config "workload=encode k=10 p=4 len=1048576 stripes=1024" --command "rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline"
@@ -88,14 +88,14 @@ for s in $STEPS; do
                 run pmc_write_c2 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write_c2" -o w -- python3 bench.py --no-cpu-baseline --steps 3 --warmup 1
                 python3 tools/pmc_csv.py "$OUT/pmc_c2_encode.csv" "workload=encode k=10 p=4 len=1048576 stripes=1024" "python bench.py --steps 3 --warmup 1 --no-cpu-baseline" "$OUT/pmc_fetch_c2" "$OUT/pmc_write_c2" ec_encode_v16
                 run pmc_sq_c2 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_SALU SQ_INSTS_SMEM SQ_WAIT_INST_ANY --output-format csv -d "$OUT/pmc_sq_c2" -o s -- python3 bench.py --no-cpu-baseline --steps 2 --warmup 1
-                run bench_decode 300 python bench.py --workload decode --cpu-seconds 5
+                run bench_decode 300 python bench.py --full --workload decode --cpu-seconds 5
                 cp "$OUT/bench_decode.log" "$OUT/bench_decode.json"
                 run rocprof_decode 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_decode" -o decode -- python3 bench.py --workload decode --no-cpu-baseline
                 run steady_decode 60 python3 tools/kernel_stats.py "$OUT/prof_decode" "ec_encode_v16<3" --skip 5 --keep 20 --bytes 13958643712 --out "$OUT/decode_encode_kernel_steady.csv" --config "workload=decode k=10 p=4 len=1048576 stripes=1024" --command "rocprofv3 --kernel-trace --stats -- python3 bench.py --workload decode --no-cpu-baseline"
                 run pmc_fetch_decode 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch_decode" -o f -- python3 bench.py --workload decode --no-cpu-baseline --steps 3 --warmup 1
                 run pmc_write_decode 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write_decode" -o w -- python3 bench.py --workload decode --no-cpu-baseline --steps 3 --warmup 1
                 python3 tools/pmc_csv.py "$OUT/pmc_decode.csv" "workload=decode k=10 p=4 len=1048576 stripes=1024" "python bench.py --workload decode --steps 3 --warmup 1 --no-cpu-baseline" "$OUT/pmc_fetch_decode" "$OUT/pmc_write_decode" ec_encode_v16
-                run bench_c2_final 300 python bench.py --no-cpu-baseline
+                run bench_c2_final 300 python bench.py --full --no-cpu-baseline
                 cp "$OUT/bench_c2_final.log" "$OUT/bench_c2_final.json"
                 ;;
         wide)
@@ -105,7 +105,7 @@ for s in $STEPS; do
                         tag=k$1p$2
                         args="--workload encode --k $1 --p $2 --len $3 --stripes $4 --no-cpu-baseline"
                         bytes=$(( ($1 + $2) * $3 * $4 ))
-                        run bench_$tag 300 python bench.py $args
+                        run bench_$tag 300 python bench.py --full $args
                         cp "$OUT/bench_$tag.log" "$OUT/bench_$tag.json"
                         run rocprof_$tag 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$tag" -o $tag -- python3 bench.py $args
                         run steady_$tag 60 python3 tools/kernel_stats.py "$OUT/prof_$tag" ec_encode_ --skip 5 --keep 20 --bytes $bytes --out "$OUT/${tag}_encode_kernel_steady.csv" --config "workload=encode k=$1 p=$2 len=$3 stripes=$4" --command "rocprofv3 --kernel-trace --stats -- python3 bench.py $args"
@@ -122,7 +122,7 @@ for s in $STEPS; do
                         for shape in ${XOR_SHAPES:-10_4_1048576_1024 20_6_4194304_64 10_8_1048576_1024 10_6_1048576_1024}; do
                                 set -- ${shape//_/ }
                                 for x in 0 1; do
-                                        ISAL_HIP_ENC_XOR=$x run bench_k$1p$2_x${x}_r$r 300 python bench.py --workload encode --k $1 --p $2 --len $3 --stripes $4 --no-cpu-baseline
+                                        ISAL_HIP_ENC_XOR=$x run bench_k$1p$2_x${x}_r$r 300 python bench.py --full --workload encode --k $1 --p $2 --len $3 --stripes $4 --no-cpu-baseline
                                 done
                         done
                 done
@@ -134,12 +134,12 @@ for s in $STEPS; do
                         for shape in ${XOR_SHAPES:-10_4_1048576_1024 20_6_4194304_64 10_8_1048576_1024 10_6_1048576_1024}; do
                                 set -- ${shape//_/ }
                                 for x in 0 1; do
-                                        ISAL_HIP_ENC_LDS=$x run bench_k$1p$2_lds${x}_r$r 300 python bench.py --workload encode --k $1 --p $2 --len $3 --stripes $4 --no-cpu-baseline
+                                        ISAL_HIP_ENC_LDS=$x run bench_k$1p$2_lds${x}_r$r 300 python bench.py --full --workload encode --k $1 --p $2 --len $3 --stripes $4 --no-cpu-baseline
                                 done
                         done
                 done
-                run bench_decode 300 python bench.py --workload decode --no-cpu-baseline
-                ISAL_HIP_ENC_LDS=0 run bench_decode_lds0 300 python bench.py --workload decode --no-cpu-baseline
+                run bench_decode 300 python bench.py --full --workload decode --no-cpu-baseline
+                ISAL_HIP_ENC_LDS=0 run bench_decode_lds0 300 python bench.py --full --workload decode --no-cpu-baseline
                 ;;
         group)
                 # encode load group forced (ISAL_HIP_ENC_GROUP) x LDS halves, wide shapes
@@ -148,7 +148,7 @@ for s in $STEPS; do
                         for v in ${GROUP_CASES:-10_8_1048576_1024_10_d 10_8_1048576_1024_5_d 10_8_1048576_1024_5_1 10_8_1048576_1024_10_1 20_6_4194304_64_10_d 20_6_4194304_64_5_d 20_6_4194304_64_4_d 10_4_1048576_1024_10_d 10_4_1048576_1024_5_d}; do
                                 set -- ${v//_/ }
                                 lds=$6; [ "$lds" = d ] && lds=
-                                ISAL_HIP_ENC_GROUP=$5 ISAL_HIP_ENC_LDS=$lds run bench_k$1p$2_g$5_l$6_r$r 300 python bench.py --workload encode --k $1 --p $2 --len $3 --stripes $4 --no-cpu-baseline
+                                ISAL_HIP_ENC_GROUP=$5 ISAL_HIP_ENC_LDS=$lds run bench_k$1p$2_g$5_l$6_r$r 300 python bench.py --full --workload encode --k $1 --p $2 --len $3 --stripes $4 --no-cpu-baseline
                         done
                 done
                 ;;
@@ -172,7 +172,7 @@ for s in $STEPS; do
                         for shape in ${WIDE5_SHAPES:-10_6_1048576_1024 10_7_1048576_1024 10_8_1048576_1024 20_6_4194304_64 20_8_4194304_64 15_6_1048576_1024 30_6_1048576_512}; do
                                 set -- ${shape//_/ }
                                 for x in 0 1; do
-                                        ISAL_HIP_ENC_WIDE5=$x run bench_k$1p$2_w${x}_r$r 300 python bench.py --workload encode --k $1 --p $2 --len $3 --stripes $4 --no-cpu-baseline
+                                        ISAL_HIP_ENC_WIDE5=$x run bench_k$1p$2_w${x}_r$r 300 python bench.py --full --workload encode --k $1 --p $2 --len $3 --stripes $4 --no-cpu-baseline
                                 done
                         done
                 done
@@ -184,7 +184,7 @@ for s in $STEPS; do
                 run pytest_gpu_confirm 600 python -u -m pytest tests -m gpu -x -q -k "xor_fast_path or load_groups or random_shapes or decode or raid or golden or kernel_label or smoke" --timeout 300 --timeout-method thread
                 for w in "encode" "decode" "encode --k 20 --p 6 --len 4194304 --stripes 64" "encode --k 10 --p 2" "encode --k 10 --p 8"; do
                         tag=$(echo $w | tr -d ' -' | cut -c1-24)
-                        run bench_${tag}_default 300 python bench.py --workload $w --no-cpu-baseline
+                        run bench_${tag}_default 300 python bench.py --full --workload $w --no-cpu-baseline
                 done
                 ;;
         ldsinfo)
@@ -219,24 +219,24 @@ for s in $STEPS; do
                         run dropin_t$t 120 tools/dropin_bench 10 4 1048576 64 $t 3
                 done
                 run dropin_small_t1 120 tools/dropin_bench 10 4 4096 64 1 3
-                run bench_dropin 300 python bench.py --workload dropin
-                ISAL_HIP_KARG=0 run bench_dropin_nokarg 300 python bench.py --workload dropin
+                run bench_dropin 300 python bench.py --full --workload dropin
+                ISAL_HIP_KARG=0 run bench_dropin_nokarg 300 python bench.py --full --workload dropin
                 run dropin_hiptrace 200 rocprofv3 --hip-trace --kernel-trace --stats --output-format csv -d "$OUT/prof_dropin" -o dropin -- tools/dropin_bench 10 4 1048576 64 1 0 400
                 ;;
         tests_crc)
                 run pytest_gpu_crc 300 python -u -m pytest tests -m gpu -x -v -k "crc" --timeout 200 --timeout-method thread
                 ;;
         bench)
-                run bench_c2 300 python bench.py
+                run bench_c2 300 python bench.py --full
                 cp "$OUT/bench_c2.log" "$OUT/bench_c2.json"
                 ;;
         crc)
-                run bench_encode_crc 300 python bench.py --workload encode-crc
-                run bench_crc 300 python bench.py --workload crc --cpu-seconds 5
+                run bench_encode_crc 300 python bench.py --full --workload encode-crc
+                run bench_crc 300 python bench.py --full --workload crc --cpu-seconds 5
                 ;;
         crc64)
                 run pytest_gpu_crc64 300 python -u -m pytest tests -m gpu -x -v -k "crc64" --timeout 200 --timeout-method thread
-                run bench_crc64 300 python bench.py --workload crc64 --cpu-seconds 5
+                run bench_crc64 300 python bench.py --full --workload crc64 --cpu-seconds 5
                 run rocprof_crc64 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_crc64" -o crc64 -- python3 bench.py --workload crc64 --no-cpu-baseline
                 run pmc_fetch_crc64 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch_crc64" -o f -- python3 bench.py --workload crc64 --no-cpu-baseline --steps 3 --warmup 1
                 run pmc_write_crc64 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write_crc64" -o w -- python3 bench.py --workload crc64 --no-cpu-baseline --steps 3 --warmup 1
@@ -245,7 +245,7 @@ for s in $STEPS; do
                 ;;
         encrc64)
                 run pytest_gpu_encrc64 300 python -u -m pytest tests -m gpu -x -v -k "encode_crc64" --timeout 200 --timeout-method thread
-                run bench_encode_crc64 300 python bench.py --workload encode-crc64 --cpu-seconds 5
+                run bench_encode_crc64 300 python bench.py --full --workload encode-crc64 --cpu-seconds 5
                 run rocprof_encrc64 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_encrc64" -o encrc64 -- python3 bench.py --workload encode-crc64 --no-cpu-baseline
                 run pmc_fetch_encrc64 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch_encrc64" -o f -- python3 bench.py --workload encode-crc64 --no-cpu-baseline --steps 3 --warmup 1
                 run pmc_write_encrc64 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write_encrc64" -o w -- python3 bench.py --workload encode-crc64 --no-cpu-baseline --steps 3 --warmup 1
@@ -256,8 +256,8 @@ for s in $STEPS; do
                 run pytest_gpu_crc 700 python -u -m pytest tests -m gpu -x -v -k "crc" --timeout 200 --timeout-method thread
                 for wl in encode-crc encode-crc64; do
                         for r in 1 2; do
-                                ISAL_HIP_LIB=isa-l_amd/lib/prev/libisal_hip.so run bench_${wl}_prev$r 300 python bench.py --workload $wl --no-cpu-baseline
-                                run bench_${wl}_new$r 300 python bench.py --workload $wl --no-cpu-baseline
+                                ISAL_HIP_LIB=isa-l_amd/lib/prev/libisal_hip.so run bench_${wl}_prev$r 300 python bench.py --full --workload $wl --no-cpu-baseline
+                                run bench_${wl}_new$r 300 python bench.py --full --workload $wl --no-cpu-baseline
                         done
                 done
                 ;;
@@ -265,7 +265,7 @@ for s in $STEPS; do
                 # checksum-only kernels: tiles per workgroup now that they are memory-side bound
                 for tt in ${TT_LIST:-16 32 64 128}; do
                         for wl in crc crc64 encode-crc encode-crc64; do
-                                ISAL_HIP_CRC_TILES=$tt run bench_${wl}_tt$tt 300 python bench.py --workload $wl --no-cpu-baseline
+                                ISAL_HIP_CRC_TILES=$tt run bench_${wl}_tt$tt 300 python bench.py --full --workload $wl --no-cpu-baseline
                         done
                 done
                 ;;
@@ -287,18 +287,18 @@ for s in $STEPS; do
                 done
                 python3 tools/pmc_csv.py "$OUT/pmc_c2_encode_crc.csv" "workload=encode-crc k=10 p=4 len=1048576 stripes=1024" "python bench.py --workload encode-crc --steps 3 --warmup 1 --no-cpu-baseline" "$OUT/pmc_fetch_encode-crc" "$OUT/pmc_write_encode-crc" ec_encode_crc_v16
                 python3 tools/pmc_csv.py "$OUT/pmc_c2_encode_crc64.csv" "workload=encode-crc64 k=10 p=4 len=1048576 stripes=1024" "python bench.py --workload encode-crc64 --steps 3 --warmup 1 --no-cpu-baseline" "$OUT/pmc_fetch_encode-crc64" "$OUT/pmc_write_encode-crc64" ec_encode_crc64_v16
-                run bench_encode_crc 300 python bench.py --workload encode-crc --cpu-seconds 5
-                run bench_encode_crc64 300 python bench.py --workload encode-crc64 --cpu-seconds 5
+                run bench_encode_crc 300 python bench.py --full --workload encode-crc --cpu-seconds 5
+                run bench_encode_crc64 300 python bench.py --full --workload encode-crc64 --cpu-seconds 5
                 ;;
         decode)
-                run bench_decode 300 python bench.py --workload decode --no-cpu-baseline
+                run bench_decode 300 python bench.py --full --workload decode --no-cpu-baseline
                 ;;
         update)
-                run bench_update 300 python bench.py --workload update --k 20 --p 6 --len 4194304 --stripes 64 --no-cpu-baseline
+                run bench_update 300 python bench.py --full --workload update --k 20 --p 6 --len 4194304 --stripes 64 --no-cpu-baseline
                 ;;
         e2e)
-                run bench_e2e_update 300 python bench.py --workload e2e-update --k 20 --p 6 --len 4194304 --steps 40 --warmup 4
-                run bench_e2e_encode 300 python bench.py --workload e2e-encode --steps 200 --warmup 10
+                run bench_e2e_update 300 python bench.py --full --workload e2e-update --k 20 --p 6 --len 4194304 --steps 40 --warmup 4
+                run bench_e2e_encode 300 python bench.py --full --workload e2e-encode --steps 200 --warmup 10
                 ;;
         prof)
                 run rocprof_c2 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_c2" -o c2 -- python3 bench.py --no-cpu-baseline
@@ -344,7 +344,7 @@ for s in $STEPS; do
                 else
                         wl=update; args="--workload update --k 20 --p 6 --len 4194304 --stripes 64"; kern=ec_update_v16; cfg="workload=update k=20 p=6 len=4194304 stripes=64"
                 fi
-                run bench_$wl 300 python bench.py $args --cpu-seconds 5
+                run bench_$wl 300 python bench.py --full $args --cpu-seconds 5
                 cp "$OUT/bench_$wl.log" "$OUT/bench_$wl.json"
                 run rocprof_$wl 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$wl" -o $wl -- python3 bench.py $args --no-cpu-baseline
                 if [ $s = updateprof ]; then
@@ -355,11 +355,11 @@ for s in $STEPS; do
                 python3 tools/pmc_csv.py "$OUT/pmc_$wl.csv" "$cfg" "python bench.py $args --steps 3 --warmup 1 --no-cpu-baseline" "$OUT/pmc_fetch_$wl" "$OUT/pmc_write_$wl" $kern
                 ;;
         c5)
-                run bench_c5 600 python bench.py --total-stripes 1048576 --steps 2 --warmup 1
+                run bench_c5 600 python bench.py --full --total-stripes 1048576 --steps 2 --warmup 1
                 cp "$OUT/bench_c5.log" "$OUT/bench_c5.json"
                 ;;
         c1)
-                run bench_c1 120 python bench.py --workload c1
+                run bench_c1 120 python bench.py --full --workload c1
                 ;;
         zc)
                 run zc_probe 300 python tools/zc_probe.py
@@ -376,13 +376,13 @@ for s in $STEPS; do
                 ;;
         crcbench)
                 for wl in encode-crc encode-crc64 crc crc64; do
-                        run bench_$wl 300 python bench.py --workload $wl --no-cpu-baseline
+                        run bench_$wl 300 python bench.py --full --workload $wl --no-cpu-baseline
                 done
                 ;;
         ttsweep)
                 for tt in ${TT_LIST:-8 16 32 64}; do
                         for wl in encode-crc64 encode-crc crc64; do
-                                ISAL_HIP_CRC_TILES=$tt run bench_${wl}_tt$tt 300 python bench.py --workload $wl --no-cpu-baseline
+                                ISAL_HIP_CRC_TILES=$tt run bench_${wl}_tt$tt 300 python bench.py --full --workload $wl --no-cpu-baseline
                         done
                 done
                 ;;
@@ -393,12 +393,12 @@ for s in $STEPS; do
                 ;;
         e2ering)
                 for dr in 2:4 2:12 6:6 6:12 3:3; do
-                        run bench_e2e_encode_d${dr%:*}_r${dr#*:} 300 python bench.py --workload e2e-encode --steps 200 --warmup 10 --depth ${dr%:*} --ring ${dr#*:}
+                        run bench_e2e_encode_d${dr%:*}_r${dr#*:} 300 python bench.py --full --workload e2e-encode --steps 200 --warmup 10 --depth ${dr%:*} --ring ${dr#*:}
                 done
                 ;;
         e2esweep)
                 for dp in ${E2E_DEPTHS:-2 3 4 6}; do
-                        run bench_e2e_encode_d$dp 300 python bench.py --workload e2e-encode --steps 200 --warmup 10 --depth $dp
+                        run bench_e2e_encode_d$dp 300 python bench.py --full --workload e2e-encode --steps 200 --warmup 10 --depth $dp
                 done
                 ;;
         *)
