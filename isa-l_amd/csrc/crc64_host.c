@@ -291,19 +291,6 @@ isal_hip_crc64_tables(int variant, long long len, int tt, uint64_t *tabs)
         chunk_tables(basis, tabs + ISAL_HIP_CRC64_CHUNK_TAB);
         isal_hip_crc64_zpow(variant, ISAL_HIP_CRC_TILE, m);
         op_tables(m, tabs + ISAL_HIP_CRC64_SHIFT_TAB);
-        /* multi-tile chain step: chunk maps followed by m tiles, Z^(4096*2), Z^(4096*4) */
-        for (s = 1; s <= 3; s++) {
-                uint64_t bm[128];
-                isal_hip_crc64_zpow(variant, (unsigned long long) ISAL_HIP_CRC_TILE * s, m);
-                for (j = 0; j < 128; j++)
-                        bm[j] = apply(m, basis[j]);
-                chunk_tables(bm, tabs + ISAL_HIP_CRC64_CHUNKX_TAB +
-                                         (s - 1) * ISAL_HIP_CRC64_CHUNK_ENTRIES);
-        }
-        isal_hip_crc64_zpow(variant, 2ULL * ISAL_HIP_CRC_TILE, m);
-        op_tables(m, tabs + ISAL_HIP_CRC64_SHIFTX_TAB);
-        isal_hip_crc64_zpow(variant, 4ULL * ISAL_HIP_CRC_TILE, m);
-        op_tables(m, tabs + ISAL_HIP_CRC64_SHIFTX_TAB + ISAL_HIP_CRC64_OP_ENTRIES);
         /* combine plan */
         isal_hip_crc64_len_tables(variant, len, tt, tabs);
         for (s = 0; s < 8; s++) {

@@ -166,25 +166,6 @@ isal_hip_crc32c_pre_tables(const uint32_t *tabs, uint32_t *out)
                 out[e] = isal_hip_crc32c_mulmod(tabs[ISAL_HIP_CRC_CHUNK_TAB + e], z);
 }
 
-/* Tables of the multi-tile chain step from the base tables: every entry of a
- * chunk map shifted by m tiles is entry * x^(8*4096*m) mod P; Z^(4096*4) of a
- * field value is its Z^4096 entry shifted by three more tiles. */
-void
-isal_hip_crc32c_ext_tables(const uint32_t *tabs, uint32_t *ext)
-{
-        int m, e;
-        const uint32_t z3 = isal_hip_crc32c_xpow8n(3ULL * ISAL_HIP_CRC_TILE);
-        for (m = 1; m <= 3; m++) {
-                const uint32_t zm = isal_hip_crc32c_xpow8n((unsigned long long) m * ISAL_HIP_CRC_TILE);
-                for (e = 0; e < ISAL_HIP_CRC_CHUNK_DWORDS; e++)
-                        ext[(m - 1) * ISAL_HIP_CRC_CHUNK_DWORDS + e] =
-                                isal_hip_crc32c_mulmod(tabs[ISAL_HIP_CRC_CHUNK_TAB + e], zm);
-        }
-        for (e = 0; e < ISAL_HIP_CRC_FIELDS * 32; e++)
-                ext[3 * ISAL_HIP_CRC_CHUNK_DWORDS + e] =
-                        isal_hip_crc32c_mulmod(tabs[ISAL_HIP_CRC_SHIFT_TAB + e], z3);
-}
-
 /* Geometry of the per-lane partials for shards of `len` bytes, `tt` tiles per
  * workgroup (see isal_hip_internal.h). */
 void
@@ -202,25 +183,46 @@ isal_hip_crc_geometry(long long len, int tt, isal_hip_crc_geom *g)
 }
 
 /* Combine constants (ISAL_HIP_CRC_PLAN_DWORDS), see crc32c_combine:
- *   [0,1024)      byte tables of x^(8*4096*tt)          (Horner across blocks)
- *   [1024,2048)   byte tables of x^(8*4096*nfull_last)  (the last block)
- *   [2048,2304)   W[L]  = x^(8*(16*(255-L) + tail))    (lane L of a full tile -> shard end)
- *   [2304,2560)   Ct[L] = x^(8*max(0, tail-16L-16))     (lane L of the ragged tile -> shard end)
- *   [2560]        x^(8*len)                             (the caller's init_crc) */
+ *   PLAN_BLOCK [0,1024)     byte tables of x^(8*4096*tt)          (Horner across blocks)
+ *   PLAN_LAST  [1024,2048)  byte tables of x^(8*4096*nfull_last)  (the last block)
+ *   PLAN_W     [2048,2304)  W[L]  = x^(8*(16*(255-L) + tail))    (lane L of a full tile -> shard end)
+ *   PLAN_CT    [2304,2560)  Ct[L] = x^(8*max(0, tail-16L-16))     (lane L of the ragged tile -> shard end)
+ *   PLAN_XLEN  [2560]       x^(8*len)                             (the caller's init_crc) */
 void
 isal_hip_crc32c_plan(long long len, int tt, uint32_t *plan)
 {
         isal_hip_crc_geom g;
         int l;
         isal_hip_crc_geometry(len, tt, &g);
-        mul_tables(isal_hip_crc32c_xpow8n((unsigned long long) ISAL_HIP_CRC_TILE * tt), plan);
+        mul_tables(isal_hip_crc32c_xpow8n((unsigned long long) ISAL_HIP_CRC_TILE * tt),
+                   plan + ISAL_HIP_CRC_PLAN_BLOCK);
         mul_tables(isal_hip_crc32c_xpow8n((unsigned long long) ISAL_HIP_CRC_TILE * g.nfull_last),
-                   plan + 1024);
+                   plan + ISAL_HIP_CRC_PLAN_LAST);
         for (l = 0; l < 256; l++) {
                 const long long rest = (long long) g.tail - 16 * l - 16;
-                plan[2048 + l] = isal_hip_crc32c_xpow8n((unsigned long long) (16 * (255 - l) + g.tail));
-                plan[2304 + l] = isal_hip_crc32c_xpow8n((unsigned long long) (rest > 0 ? rest : 0));
+                plan[ISAL_HIP_CRC_PLAN_W + l] =
+                        isal_hip_crc32c_xpow8n((unsigned long long) (16 * (255 - l) + g.tail));
+                plan[ISAL_HIP_CRC_PLAN_CT + l] =
+                        isal_hip_crc32c_xpow8n((unsigned long long) (rest > 0 ? rest : 0));
         }
-        plan[2560] = isal_hip_crc32c_xpow8n((unsigned long long) len);
-        plan[2561] = plan[2562] = plan[2563] = 0;
+        plan[ISAL_HIP_CRC_PLAN_XLEN] = isal_hip_crc32c_xpow8n((unsigned long long) len);
+        for (l = ISAL_HIP_CRC_PLAN_XLEN + 1; l < ISAL_HIP_CRC_PLAN_DWORDS; l++)
+                plan[l] = 0;
+}
+
+/* The device image (ISAL_HIP_CRC_IMAGE_DWORDS): the part that depends on the
+ * length and the geometry, then the whole. */
+void
+isal_hip_crc32c_image_len(long long len, int tt, uint32_t *out)
+{
+        isal_hip_crc32c_plan(len, tt, out + ISAL_HIP_CRC_TAB_DWORDS);
+}
+
+void
+isal_hip_crc32c_image(long long len, int tt, uint32_t *out)
+{
+        isal_hip_crc32c_tables(out);
+        isal_hip_crc32c_image_len(len, tt, out);
+        isal_hip_crc32c_byte_tables(out + ISAL_HIP_CRC_B16_TAB);
+        isal_hip_crc32c_pre_tables(out, out + ISAL_HIP_CRC_FPRE_TAB);
 }

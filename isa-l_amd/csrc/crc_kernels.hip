@@ -306,20 +306,20 @@ __global__ __launch_bounds__(kBlock) void crc32c_combine(
     const uint32_t* __restrict__ plan, unsigned nblk, int has_tail, unsigned init,
     uint32_t* __restrict__ out, unsigned nsh) {
   constexpr unsigned kWaves = kBlock / 64;
-  __shared__ uint32_t kt[2048];
-  for (int i = threadIdx.x; i < 2048; i += kBlock) kt[i] = plan[i];
+  __shared__ uint32_t kt[ISAL_HIP_CRC_PLAN_W];  // both byte tables: PLAN_BLOCK, PLAN_LAST
+  for (int i = threadIdx.x; i < ISAL_HIP_CRC_PLAN_W; i += kBlock) kt[i] = plan[i];
   __syncthreads();
   const unsigned lane = threadIdx.x & 63;
-  const uint4 wl = reinterpret_cast<const uint4*>(plan + 2048)[lane];
-  const uint4 cl = reinterpret_cast<const uint4*>(plan + 2304)[lane];
-  const uint32_t xlen = plan[2560];
+  const uint4 wl = reinterpret_cast<const uint4*>(plan + ISAL_HIP_CRC_PLAN_W)[lane];
+  const uint4 cl = reinterpret_cast<const uint4*>(plan + ISAL_HIP_CRC_PLAN_CT)[lane];
+  const uint32_t xlen = plan[ISAL_HIP_CRC_PLAN_XLEN];
   const uint32_t w4[4] = {wl.x, wl.y, wl.z, wl.w}, c4[4] = {cl.x, cl.y, cl.z, cl.w};
   const uint32_t iterm = crc_mulmod(init, xlen);
   for (unsigned sh = blockIdx.x * kWaves + (threadIdx.x >> 6); sh < nsh; sh += gridDim.x * kWaves) {
     const uint32_t* pp = part + static_cast<size_t>(sh) * nblk * kBlock + 4 * lane;
     uint32_t h[4] = {0, 0, 0, 0};
     for (unsigned b = 0; b < nblk; ++b) {
-      const uint32_t* k4 = (b + 1 == nblk) ? kt + 1024 : kt;
+      const uint32_t* k4 = (b + 1 == nblk) ? kt + ISAL_HIP_CRC_PLAN_LAST : kt + ISAL_HIP_CRC_PLAN_BLOCK;
       const uint4 p = *reinterpret_cast<const uint4*>(pp + static_cast<size_t>(b) * kBlock);
       const uint32_t pv[4] = {p.x, p.y, p.z, p.w};
 #pragma unroll

@@ -1,6 +1,7 @@
 /*
  * isal_hip_internal.h — contract between the C host shim (isal_hip_shim.c,
- * gf_host.c) and the HIP kernel launchers (ec_kernels.hip). Not installed.
+ * the batch API in isal_hip_batch.c, gf_host.c) and the HIP kernel launchers
+ * (ec_kernels.hip). Not installed.
  *
  * Device argument layout (one contiguous device allocation per call or batch):
  *
@@ -178,6 +179,40 @@ typedef struct {
 } isal_hip_xrows;
 void isal_hip_xor_rows(int k, int rows, const unsigned char *gftbls, isal_hip_xrows *x);
 
+/* Device allocations already seen by one call: a shard inside one of them is
+ * device memory too, with no HIP query (a stripe's shards usually come from
+ * one or two allocations: 14 queries of ~0.4 us become one or two). Only
+ * within one call — a later call may find the memory freed and reused. */
+#define SEEN_MAX 4
+typedef struct {
+        int n;
+        uintptr_t lo[SEEN_MAX], hi[SEEN_MAX];
+        int dev[SEEN_MAX];
+} seen_t;
+
+/* the device of the seen allocation holding [p, p + len), or -1 */
+static inline int
+seen_dev(const seen_t *sn, const void *p, size_t len)
+{
+        const uintptr_t a = (uintptr_t) p;
+        int i;
+        for (i = 0; i < sn->n; i++)
+                if (a >= sn->lo[i] && a < sn->hi[i] && len <= sn->hi[i] - a)
+                        return sn->dev[i];
+        return -1;
+}
+
+static inline void
+seen_add(seen_t *sn, uintptr_t base, size_t size, int dev)
+{
+        if (size && dev >= 0 && sn->n < SEEN_MAX) {
+                sn->lo[sn->n] = base;
+                sn->hi[sn->n] = base + size;
+                sn->dev[sn->n] = dev;
+                sn->n++;
+        }
+}
+
 /* Make dev the calling thread's current device for a call on an object that
  * belongs to it; returns what isal_hip_dev_leave restores (-1: nothing, -2:
  * the switch failed). */
@@ -256,18 +291,22 @@ unsigned long long isal_cpu_run(int op, long long c0, int len, int k, int rows, 
 #define ISAL_HIP_CRC_CHUNK_TAB 256
 #define ISAL_HIP_CRC_SHIFT_TAB (ISAL_HIP_CRC_CHUNK_TAB + 4 * ISAL_HIP_CRC_FIELDS * 32)
 #define ISAL_HIP_CRC_TAB_DWORDS (ISAL_HIP_CRC_SHIFT_TAB + ISAL_HIP_CRC_FIELDS * 32)
-#define ISAL_HIP_CRC_PLAN_DWORDS (2 * 1024 + 2 * 256 + 4)
-/* Multi-tile chain step of crc32c_shards, stored after the plan:
- * Z^(4096*m) o crc(0, chunk) for m = 1..3, then Z^(4096*4). */
 #define ISAL_HIP_CRC_CHUNK_DWORDS (4 * ISAL_HIP_CRC_FIELDS * 32)
-#define ISAL_HIP_CRC_EXT_TAB (ISAL_HIP_CRC_TAB_DWORDS + ISAL_HIP_CRC_PLAN_DWORDS)
-#define ISAL_HIP_CRC_EXT_DWORDS (3 * ISAL_HIP_CRC_CHUNK_DWORDS + ISAL_HIP_CRC_FIELDS * 32)
-/* Byte-position tables of the fused kernel's byte path, after EXT:
+/* The combine plan (isal_hip_crc32c_plan, read by crc32c_combine) follows the
+ * base tables, at ISAL_HIP_CRC_TAB_DWORDS: the only part of the device image
+ * that depends on the length and the block geometry. Offsets within it: */
+#define ISAL_HIP_CRC_PLAN_BLOCK 0   /* byte tables of x^(8*4096*tt) */
+#define ISAL_HIP_CRC_PLAN_LAST 1024 /* byte tables of x^(8*4096*nfull_last) */
+#define ISAL_HIP_CRC_PLAN_W 2048    /* W[L], 256 lanes */
+#define ISAL_HIP_CRC_PLAN_CT 2304   /* Ct[L], 256 lanes */
+#define ISAL_HIP_CRC_PLAN_XLEN 2560 /* x^(8*len), then 3 words of padding */
+#define ISAL_HIP_CRC_PLAN_DWORDS (ISAL_HIP_CRC_PLAN_XLEN + 4)
+/* Byte-position tables of the fused kernel's byte path, after the plan:
  *   P:  table p (byte p of a 16-byte chunk) = crc of byte b followed by
  *       15 - p zero bytes, 16 x 256 dwords;
  *   P': the same followed by 4080 more zero bytes (Z^4080 o P: the step of a
  *       pre-shifted chain, crc_kernels.hip). */
-#define ISAL_HIP_CRC_B16_TAB (ISAL_HIP_CRC_EXT_TAB + ISAL_HIP_CRC_EXT_DWORDS)
+#define ISAL_HIP_CRC_B16_TAB (ISAL_HIP_CRC_TAB_DWORDS + ISAL_HIP_CRC_PLAN_DWORDS)
 #define ISAL_HIP_CRC_B16_DWORDS (2 * 16 * 256)
 void isal_hip_crc32c_byte_tables(uint32_t *out);
 /* F' = Z^4080 o crc(0, chunk) as field tables (the layout of CHUNK_TAB), for
@@ -275,6 +314,13 @@ void isal_hip_crc32c_byte_tables(uint32_t *out);
 #define ISAL_HIP_CRC_FPRE_TAB (ISAL_HIP_CRC_B16_TAB + ISAL_HIP_CRC_B16_DWORDS)
 #define ISAL_HIP_CRC_FPRE_DWORDS ISAL_HIP_CRC_CHUNK_DWORDS
 void isal_hip_crc32c_pre_tables(const uint32_t *tabs, uint32_t *out);
+/* The whole device image: base tables, plan, B16, F'. isal_hip_crc32c_image
+ * builds all of it for shards of len bytes at tt tiles per workgroup;
+ * isal_hip_crc32c_image_len only the part that depends on len and tt (the
+ * plan), at its place in out — as isal_hip_crc64_len_tables does for CRC64. */
+#define ISAL_HIP_CRC_IMAGE_DWORDS (ISAL_HIP_CRC_FPRE_TAB + ISAL_HIP_CRC_FPRE_DWORDS)
+void isal_hip_crc32c_image(long long len, int tt, uint32_t *out);
+void isal_hip_crc32c_image_len(long long len, int tt, uint32_t *out);
 #define ISAL_HIP_CRC_MAX_FUSED_K 64 /* fused encode keeps k source partials in LDS */
 
 typedef struct {
@@ -285,6 +331,11 @@ typedef struct {
         long long nblk;   /* workgroups per shard */
         long long nfull_last; /* full tiles in the last workgroup */
 } isal_hip_crc_geom;
+
+/* Tiles per CRC workgroup (CRC32C and CRC64) of a launch over nstripes
+ * stripes of len-byte shards: def, halved for small launches;
+ * ISAL_HIP_CRC_TILES overrides (isal_hip_batch.c). */
+int isal_hip_crc_tiles(int len, int nstripes, int def);
 
 /* ---- CRC64 of shards (crc64_host.c, crc64_kernels.hip) ---------------------
  * The eight crc64_* flavours (reference include/crc64.h:54-163). Same lane
@@ -299,8 +350,6 @@ typedef struct {
  *   OP_BLOCK   Z^(4096*tt)   OP_LAST Z^(4096*nfull_last)
  *   OP_TREE    Z^(16 * 2^s), s = 0..7 (lane tree)   OP_TAIL Z^(16*(tail/16))
  *   (crc64_combine loads BYTE..OP_TAIL: COMBINE_ENTRIES)
- *   CHUNKX_TAB Z^(4096*m) o raw(0, chunk), m = 1..3 (multi-tile chain step)
- *   SHIFTX_TAB Z^8192, Z^16384
  *   SLICE_TAB  slicing-by-8 tables of the fused kernel's byte-indexed chunk
  *              path, in the "u-domain" u = pi(s) (pi = byte swap for the norm
  *              flavours, identity for refl), where processing 8 bytes d is
@@ -318,9 +367,7 @@ typedef struct {
 #define ISAL_HIP_CRC64_OP_TAIL (ISAL_HIP_CRC64_OP_TREE + 8 * ISAL_HIP_CRC64_OP_ENTRIES)
 #define ISAL_HIP_CRC64_COMBINE_ENTRIES (ISAL_HIP_CRC64_OP_TAIL + ISAL_HIP_CRC64_OP_ENTRIES)
 #define ISAL_HIP_CRC64_CHUNK_ENTRIES (4 * ISAL_HIP_CRC_FIELDS * 32)
-#define ISAL_HIP_CRC64_CHUNKX_TAB ISAL_HIP_CRC64_COMBINE_ENTRIES
-#define ISAL_HIP_CRC64_SHIFTX_TAB (ISAL_HIP_CRC64_CHUNKX_TAB + 3 * ISAL_HIP_CRC64_CHUNK_ENTRIES)
-#define ISAL_HIP_CRC64_SLICE_TAB (ISAL_HIP_CRC64_SHIFTX_TAB + 2 * ISAL_HIP_CRC64_OP_ENTRIES)
+#define ISAL_HIP_CRC64_SLICE_TAB ISAL_HIP_CRC64_COMBINE_ENTRIES
 #define ISAL_HIP_CRC64_SLICE_ENTRIES (2 * 8 * 256)
 /*   PRE_TAB    field tables of the checksum-only kernel's pre-shifted chains
  *              (u-domain): F_u = pi o raw(0, chunk), F'_u = pi o Z^4080 o raw(0, chunk) */
@@ -370,7 +417,6 @@ int isal_hip_launch_encode_crc64(const uint64_t *d_ptrs, int k, int rows, long l
 uint32_t isal_hip_crc32c_mulmod(uint32_t a, uint32_t b);
 uint32_t isal_hip_crc32c_xpow8n(unsigned long long n);
 void isal_hip_crc32c_tables(uint32_t *tabs);
-void isal_hip_crc32c_ext_tables(const uint32_t *tabs, uint32_t *ext);
 void isal_hip_crc_geometry(long long len, int tt, isal_hip_crc_geom *g);
 void isal_hip_crc32c_plan(long long len, int tt, uint32_t *plan);
 

@@ -3,7 +3,8 @@
  *
  * Exports the reference's data-path symbols (erasure_code.h, gf_vect_mul.h:
  * ec_encode_data, ec_encode_data_update, gf_vect_dot_prod, gf_vect_mad,
- * gf_vect_mul and their *_base twins) and the batched extension (isal_hip.h).
+ * gf_vect_mul and their *_base twins) and the checksum entry points (crc.h,
+ * crc64.h); the batched extension (isal_hip.h) lives in isal_hip_batch.c.
  * Replaces the reference's L2 dispatch + L3 glue (ec_multibinary.asm:79-93,
  * ec_highlevel_func.c:159-698): instead of picking a CPU ISA, calls are
  * routed to the GPU kernels in ec_kernels.hip (small host-resident calls: the
@@ -710,40 +711,6 @@ isal_hip_route_device(int n, const int *kind, const int *dev, int cur, int *bad,
                         in_place[i] = kind[i] == CL_DEVICE || kind[i] == CL_MANAGED ||
                                       (kind[i] == CL_PINNED && owner >= 0 && dev[i] == owner);
         return owner;
-}
-
-/* Device allocations already seen by one call: a shard inside one of them is
- * device memory too, with no HIP query (a stripe's shards usually come from
- * one or two allocations: 14 queries of ~0.4 us become one or two). Only
- * within one call — a later call may find the memory freed and reused. */
-#define SEEN_MAX 4
-typedef struct {
-        int n;
-        uintptr_t lo[SEEN_MAX], hi[SEEN_MAX];
-        int dev[SEEN_MAX];
-} seen_t;
-
-/* the device of the seen allocation holding [p, p + len), or -1 */
-static int
-seen_dev(const seen_t *sn, const void *p, size_t len)
-{
-        const uintptr_t a = (uintptr_t) p;
-        int i;
-        for (i = 0; i < sn->n; i++)
-                if (a >= sn->lo[i] && a < sn->hi[i] && len <= sn->hi[i] - a)
-                        return sn->dev[i];
-        return -1;
-}
-
-static void
-seen_add(seen_t *sn, uintptr_t base, size_t size, int dev)
-{
-        if (size && dev >= 0 && sn->n < SEEN_MAX) {
-                sn->lo[sn->n] = base;
-                sn->hi[sn->n] = base + size;
-                sn->dev[sn->n] = dev;
-                sn->n++;
-        }
 }
 
 /* ---- the generic synchronous call --------------------------------------- */
@@ -2078,477 +2045,6 @@ isal_hip_dev_leave(int prev)
                 (void) hipSetDevice(prev);
 }
 
-/* ---- batched extension (isal_hip.h) ------------------------------------ */
-
-struct isal_hip_batch {
-        int len, k, rows, nstripes, device, vec16;
-        uint64_t *d_ptrs;
-        uint32_t *d_tbl;
-        isal_hip_xrows xr; /* 0/1 parity rows: CRCs derived, not computed */
-        isal_hip_encmask em; /* 0/1 rows and columns: XORs instead of lookups */
-        /* CRC32C state, allocated on first use: kernel tables + combine plan,
-         * and the per-lane partials (crc_kernels.hip) */
-        uint64_t *d_ldsx; /* LDS product tables of the wide passes (NULL: not used) */
-        isal_hip_crc_geom crc;
-        uint32_t *d_crc, *d_part, *d_tail;
-        /* CRC64 state, allocated on first use: one table set per variant
-         * and pass used (never overwritten, so switching variants needs no
-         * device synchronisation) and the per-lane chains. The fused pass
-         * (c64_tt tiles per block) and the checksum-only pass (c64_tt_ck)
-         * have their own block geometry; the partials are sized for the
-         * shorter blocks. */
-        int c64_tt, c64_tt_ck;
-        uint64_t *d_c64tab[ISAL_HIP_CRC64_NVARIANTS], *d_c64tab_ck[ISAL_HIP_CRC64_NVARIANTS], *d_c64part;
-};
-
-/* Every shard of a batch on device dev: hipMalloc memory of dev, managed
- * memory, or page-locked host memory whose device address is its host address.
- * A stripe's shards usually come from a few allocations, so a device range
- * already seen answers without a HIP query. */
-static int
-batch_check_ptrs(const uint64_t *ptrs, size_t n, size_t len, int dev)
-{
-        seen_t sn;
-        size_t i;
-        sn.n = 0;
-        for (i = 0; i < n; i++) {
-                const void *p = (const void *) (uintptr_t) ptrs[i];
-                hipPointerAttribute_t a;
-                int sd;
-                if (!p)
-                        return ISAL_HIP_EINVAL;
-                if ((sd = seen_dev(&sn, p, len)) >= 0) {
-                        if (sd != dev)
-                                return ISAL_HIP_EDEVICE;
-                        continue;
-                }
-                if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-                        (void) hipGetLastError();
-                        return ISAL_HIP_EINVAL; /* pageable: no kernel can reach it */
-                }
-                if (a.type == hipMemoryTypeDevice) {
-                        hipDeviceptr_t base;
-                        size_t size;
-                        if (a.device != dev)
-                                return ISAL_HIP_EDEVICE;
-                        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t) p) == hipSuccess)
-                                seen_add(&sn, (uintptr_t) base, size, a.device);
-                        else
-                                (void) hipGetLastError();
-                } else if (a.type == hipMemoryTypeHost) {
-                        if (a.devicePointer != p)
-                                return ISAL_HIP_EINVAL;
-                } else if (a.type != hipMemoryTypeManaged && a.type != hipMemoryTypeUnified) {
-                        return ISAL_HIP_EINVAL;
-                }
-        }
-        return ISAL_HIP_OK;
-}
-
-int
-isal_hip_batch_create(isal_hip_batch **out, int len, int k, int rows, const unsigned char *gftbls,
-                      int nstripes, unsigned char *const *data, unsigned char *const *coding)
-{
-        isal_hip_batch *b;
-        uint64_t *h_ptrs;
-        long long s, stride = (long long) k + rows;
-        size_t nptr;
-        int j, vec16 = 1;
-        if (!out || len < 0 || k < 0 || rows <= 0 || nstripes <= 0 || !gftbls || !coding ||
-            (k > 0 && !data))
-                return ISAL_HIP_EINVAL;
-        *out = NULL;
-        b = (isal_hip_batch *) calloc(1, sizeof(*b));
-        nptr = (size_t) nstripes * (size_t) stride;
-        h_ptrs = (uint64_t *) malloc(nptr * 8);
-        if (!b || !h_ptrs) {
-                free(b);
-                free(h_ptrs);
-                return ISAL_HIP_ENOMEM;
-        }
-        for (s = 0; s < nstripes; s++) {
-                for (j = 0; j < k; j++)
-                        h_ptrs[s * stride + j] = (uint64_t) (uintptr_t) data[s * k + j];
-                for (j = 0; j < rows; j++)
-                        h_ptrs[s * stride + k + j] = (uint64_t) (uintptr_t) coding[s * rows + j];
-        }
-        for (s = 0; s < (long long) nptr; s++)
-                if (h_ptrs[s] & 15)
-                        vec16 = 0;
-        b->len = len;
-        b->k = k;
-        b->rows = rows;
-        b->nstripes = nstripes;
-        b->vec16 = vec16;
-        if (hipGetDevice(&b->device) != hipSuccess) {
-                free(h_ptrs);
-                isal_hip_batch_destroy(b);
-                return ISAL_HIP_EHIP;
-        }
-        if (len > 0 && (j = batch_check_ptrs(h_ptrs, nptr, (size_t) len, b->device)) != ISAL_HIP_OK) {
-                free(h_ptrs);
-                isal_hip_batch_destroy(b);
-                return j;
-        }
-        if (hipMalloc((void **) &b->d_ptrs, nptr * 8) != hipSuccess ||
-            hipMemcpy(b->d_ptrs, h_ptrs, nptr * 8, hipMemcpyHostToDevice) != hipSuccess) {
-                free(h_ptrs);
-                isal_hip_batch_destroy(b);
-                return ISAL_HIP_EHIP;
-        }
-        free(h_ptrs);
-        if (isal_hip_batch_set_tables(b, gftbls) != 0) {
-                isal_hip_batch_destroy(b);
-                return ISAL_HIP_EHIP;
-        }
-        *out = b;
-        return ISAL_HIP_OK;
-}
-
-static int
-batch_set_tables_impl(isal_hip_batch *b, const unsigned char *gftbls)
-{
-        size_t n;
-        uint32_t *h;
-        hipError_t e;
-        isal_hip_xrows xr;
-        isal_hip_encmask em;
-        if (!b || !gftbls)
-                return ISAL_HIP_EINVAL;
-        n = isal_hip_tables_dwords(b->k, b->rows);
-        h = (uint32_t *) malloc(n * 4 + 4);
-        if (!h)
-                return ISAL_HIP_ENOMEM;
-        isal_hip_build_tables(b->k, b->rows, gftbls, h);
-        /* published with the device tables only: a failed update keeps the
-         * old row masks beside the old coefficients */
-        isal_hip_xor_rows(b->k, b->rows, gftbls, &xr);
-        isal_hip_enc_masks(b->k, b->rows, gftbls, &em);
-        if (!b->d_tbl) {
-                if (hipMalloc((void **) &b->d_tbl, n * 4 + 4) != hipSuccess) {
-                        free(h);
-                        return ISAL_HIP_EHIP;
-                }
-                e = hipSuccess;
-        } else {
-                /* launches already queued on any (possibly non-blocking) stream may
-                 * still read the old coefficients: let them finish first */
-                e = hipDeviceSynchronize();
-        }
-        if (e == hipSuccess)
-                e = hipMemcpy(b->d_tbl, h, n * 4, hipMemcpyHostToDevice);
-        free(h);
-        /* the wide passes' LDS product tables (ec_encode_ldsx): k <= 64, a
-         * pass of at least 4 rows (4 only when ISAL_HIP_ENC_LDSX=1 forces it) */
-        if (e == hipSuccess && b->k >= 1 && b->k <= 64 && b->rows >= 4) {
-                const size_t nw = isal_hip_ldsx_words(b->k, b->rows);
-                uint64_t *hx = (uint64_t *) malloc(nw * 8);
-                if (!hx)
-                        return ISAL_HIP_ENOMEM;
-                isal_hip_build_ldsx_tables(b->k, b->rows, gftbls, hx);
-                if (!b->d_ldsx && hipMalloc((void **) &b->d_ldsx, nw * 8) != hipSuccess)
-                        b->d_ldsx = NULL;
-                e = b->d_ldsx ? hipMemcpy(b->d_ldsx, hx, nw * 8, hipMemcpyHostToDevice) : hipSuccess;
-                free(hx);
-        }
-        if (e != hipSuccess)
-                return ISAL_HIP_EHIP;
-        b->xr = xr;
-        b->em = em;
-        b->em.ldsx = b->d_ldsx;
-        return ISAL_HIP_OK;
-}
-
-static int
-batch_encode_impl(isal_hip_batch *b, void *stream)
-{
-        if (!b)
-                return ISAL_HIP_EINVAL;
-        return isal_hip_launch_encode(b->d_ptrs, b->k + b->rows, 0, b->k, b->d_tbl, b->len, b->k,
-                                      b->rows, b->nstripes, b->vec16, &b->em, stream)
-                       ? ISAL_HIP_EHIP
-                       : ISAL_HIP_OK;
-}
-
-static int
-batch_update_impl(isal_hip_batch *b, int vec_i, void *stream)
-{
-        if (!b || vec_i < 0 || vec_i >= b->k)
-                return ISAL_HIP_EINVAL;
-        return isal_hip_launch_update(b->d_ptrs, b->k + b->rows, vec_i, b->k, b->d_tbl, b->len,
-                                      b->k, b->rows, vec_i, b->nstripes, b->vec16, stream)
-                       ? ISAL_HIP_EHIP
-                       : ISAL_HIP_OK;
-}
-
-static int
-batch_check_impl(isal_hip_batch *b, unsigned long long *bad, void *stream)
-{
-        if (!b || !bad || !b->vec16)
-                return ISAL_HIP_EINVAL;
-        return isal_hip_launch_verify_batch(b->d_ptrs, b->k + b->rows, 0, b->k, b->d_tbl, b->len, b->k, b->rows,
-                                            b->nstripes, &b->em, bad, stream)
-                       ? ISAL_HIP_EHIP
-                       : ISAL_HIP_OK;
-}
-
-int
-isal_hip_batch_destroy(isal_hip_batch *b)
-{
-        if (!b)
-                return ISAL_HIP_OK;
-        if (b->d_ptrs)
-                (void) hipFree(b->d_ptrs);
-        if (b->d_tbl)
-                (void) hipFree(b->d_tbl);
-        if (b->d_ldsx)
-                (void) hipFree(b->d_ldsx);
-        if (b->d_crc)
-                (void) hipFree(b->d_crc);
-        if (b->d_part)
-                (void) hipFree(b->d_part);
-        for (int v = 0; v < ISAL_HIP_CRC64_NVARIANTS; v++) {
-                if (b->d_c64tab[v])
-                        (void) hipFree(b->d_c64tab[v]);
-                if (b->d_c64tab_ck[v])
-                        (void) hipFree(b->d_c64tab_ck[v]);
-        }
-        if (b->d_c64part)
-                (void) hipFree(b->d_c64part);
-        free(b);
-        return ISAL_HIP_OK;
-}
-
-/* ---- CRC32C of the batch's shards (isal_hip.h) ---------------------------- */
-
-/* Tiles per CRC workgroup: `def` (64 for both CRC32C and CRC64: 256 KiB of
- * each shard per block, partials 0.1 % (CRC32C) / 0.2 % (CRC64) of the bytes
- * — profiles/r02/r02_crc_tiles_sweep_b.jsonl, r03_crc_tiles_sweep.jsonl), halved
- * while the launch would have fewer than 2048 workgroups.
- * ISAL_HIP_CRC_TILES overrides. */
-static int
-crc_tiles(int len, int nstripes, int def)
-{
-        const long long knob = isal_hip_knob(ISAL_HIP_KNOB_CRC_TILES);
-        long long ntiles = ((long long) len + ISAL_HIP_CRC_TILE - 1) / ISAL_HIP_CRC_TILE;
-        int tt = knob >= 0 ? (int) knob : def;
-        if (tt < 1)
-                tt = 1;
-        if (knob >= 0)
-                return tt;
-        while (tt > 1 && (long long) nstripes * ((ntiles + tt - 1) / tt) < 2048)
-                tt /= 2;
-        return tt;
-}
-
-static int
-batch_crc_setup(isal_hip_batch *b)
-{
-        uint32_t *h;
-        size_t tab = ISAL_HIP_CRC_TAB_DWORDS,
-               plan = ISAL_HIP_CRC_PLAN_DWORDS + ISAL_HIP_CRC_EXT_DWORDS + ISAL_HIP_CRC_B16_DWORDS +
-                      ISAL_HIP_CRC_FPRE_DWORDS,
-               nsh, part, tail;
-        hipError_t e;
-        if (b->d_crc)
-                return ISAL_HIP_OK;
-        /* 64 tiles per block: the checksum-only pass is memory-side bound and runs
-         * 12 % faster than at 16, the fused pass is flat from 16 to 64
-         * (profiles/r02/r02_crc_tiles_sweep_b.jsonl) */
-        isal_hip_crc_geometry(b->len, crc_tiles(b->len, b->nstripes, 64), &b->crc);
-        nsh = (size_t) b->nstripes * (size_t) (b->k + b->rows);
-        part = nsh * (size_t) b->crc.nblk * 256;
-        tail = nsh * 256;
-        h = (uint32_t *) malloc((tab + plan) * 4);
-        if (!h)
-                return ISAL_HIP_ENOMEM;
-        isal_hip_crc32c_tables(h);
-        isal_hip_crc32c_plan(b->len, b->crc.tt, h + tab);
-        isal_hip_crc32c_ext_tables(h, h + ISAL_HIP_CRC_EXT_TAB);
-        isal_hip_crc32c_byte_tables(h + ISAL_HIP_CRC_B16_TAB);
-        isal_hip_crc32c_pre_tables(h, h + ISAL_HIP_CRC_FPRE_TAB);
-        e = hipMalloc((void **) &b->d_crc, (tab + plan) * 4);
-        if (e == hipSuccess)
-                e = hipMemcpy(b->d_crc, h, (tab + plan) * 4, hipMemcpyHostToDevice);
-        free(h);
-        if (e == hipSuccess)
-                e = hipMalloc((void **) &b->d_part, (part + tail) * 4);
-        if (e != hipSuccess) {
-                if (b->d_crc)
-                        (void) hipFree(b->d_crc);
-                b->d_crc = b->d_part = NULL;
-                return e == hipErrorOutOfMemory ? ISAL_HIP_ENOMEM : ISAL_HIP_EHIP;
-        }
-        b->d_tail = b->d_part + part;
-        return ISAL_HIP_OK;
-}
-
-static int
-batch_crc_finish(isal_hip_batch *b, unsigned int init, unsigned int *crc, void *stream)
-{
-        const long long nsh = (long long) b->nstripes * (b->k + b->rows);
-        return isal_hip_launch_crc_combine(b->d_part, b->d_tail, b->d_crc + ISAL_HIP_CRC_TAB_DWORDS,
-                                           b->crc.nblk, b->crc.tail != 0, init, (uint32_t *) crc,
-                                           nsh, stream)
-                       ? ISAL_HIP_EHIP
-                       : ISAL_HIP_OK;
-}
-
-static int
-batch_crc_empty(isal_hip_batch *b, unsigned int init, unsigned int *crc, void *stream)
-{
-        /* crc32_iscsi of 0 bytes is init_crc */
-        const size_t n = (size_t) b->nstripes * (size_t) (b->k + b->rows);
-        return hipMemsetD32Async((hipDeviceptr_t) crc, (int) init, n, (hipStream_t) stream) ==
-                               hipSuccess
-                       ? ISAL_HIP_OK
-                       : ISAL_HIP_EHIP;
-}
-
-static int
-batch_crc_impl(isal_hip_batch *b, unsigned int init, unsigned int *crc, void *stream)
-{
-        int r;
-        if (!b || !crc)
-                return ISAL_HIP_EINVAL;
-        if (b->len == 0)
-                return batch_crc_empty(b, init, crc, stream);
-        if ((r = batch_crc_setup(b)) != ISAL_HIP_OK)
-                return r;
-        if (isal_hip_launch_crc(b->d_ptrs, b->k + b->rows, 0, b->k + b->rows, b->nstripes, b->len,
-                                b->vec16, b->crc.tt, b->d_crc, b->d_part, b->d_tail,
-                                b->k + b->rows, 0, stream))
-                return ISAL_HIP_EHIP;
-        return batch_crc_finish(b, init, crc, stream);
-}
-
-/* ---- CRC64 of the batch's shards (isal_hip.h) ----------------------------- */
-
-/* ck: the checksum-only pass (else the fused encode + CRC64 pass). */
-static int
-batch_crc64_setup(isal_hip_batch *b, int variant, int ck)
-{
-        isal_hip_crc64_geom g;
-        uint64_t *h, *d = NULL;
-        hipError_t e;
-        const size_t tab = ISAL_HIP_CRC64_TAB_ENTRIES;
-        uint64_t **slot = ck ? &b->d_c64tab_ck[variant] : &b->d_c64tab[variant];
-        if (*slot)
-                return ISAL_HIP_OK;
-        if (!b->d_c64part && !b->c64_tt) {
-                /* Tiles per block: the fused pass 64 (flat from 32 to 64,
-                 * profiles/r03/r03_crc_tiles_sweep.jsonl; 128 is 1.2-1.6 %
-                 * slower), the checksum-only pass with its two chains per lane
-                 * 128 (+1.3-1.6 % over 64, profiles/r05/r05_crc64_tiles_ab.txt).
-                 * crc_tiles halves both alike for small batches, so c64_tt_ck
-                 * >= c64_tt and the partials sized for c64_tt hold either. */
-                b->c64_tt = crc_tiles(b->len, b->nstripes, 64);
-                b->c64_tt_ck = crc_tiles(b->len, b->nstripes, 128);
-                isal_hip_crc64_geometry(b->len, b->c64_tt < b->c64_tt_ck ? b->c64_tt : b->c64_tt_ck, &g);
-                if (g.nblk) {
-                        e = hipMalloc((void **) &b->d_c64part, (size_t) b->nstripes *
-                                                                       (size_t) (b->k + b->rows) *
-                                                                       (size_t) g.nblk * 256 * 8);
-                        if (e != hipSuccess) {
-                                b->d_c64part = NULL;
-                                b->c64_tt = b->c64_tt_ck = 0; /* retry the whole setup next time */
-                                return e == hipErrorOutOfMemory ? ISAL_HIP_ENOMEM : ISAL_HIP_EHIP;
-                        }
-                }
-        }
-        h = (uint64_t *) malloc(tab * 8);
-        if (!h)
-                return ISAL_HIP_ENOMEM;
-        isal_hip_crc64_tables(variant, b->len, ck ? b->c64_tt_ck : b->c64_tt, h);
-        /* a fresh buffer per variant: launches of other variants queued on any
-         * stream keep reading their own tables */
-        e = hipMalloc((void **) &d, tab * 8);
-        if (e == hipSuccess)
-                e = hipMemcpy(d, h, tab * 8, hipMemcpyHostToDevice);
-        free(h);
-        if (e != hipSuccess) {
-                if (d)
-                        (void) hipFree(d);
-                return e == hipErrorOutOfMemory ? ISAL_HIP_ENOMEM : ISAL_HIP_EHIP;
-        }
-        *slot = d; /* published only once filled */
-        return ISAL_HIP_OK;
-}
-
-static int
-batch_crc64_impl(isal_hip_batch *b, int variant, unsigned long long init,
-                     unsigned long long *crc, void *stream)
-{
-        int r;
-        if (!b || !crc || variant < 0 || variant >= ISAL_HIP_CRC64_NVARIANTS)
-                return ISAL_HIP_EINVAL;
-        if ((r = batch_crc64_setup(b, variant, 1)) != ISAL_HIP_OK)
-                return r;
-        return isal_hip_launch_crc64(b->d_ptrs, b->k + b->rows, b->k + b->rows, b->nstripes,
-                                     b->len, b->vec16, isal_hip_crc64_is_refl(variant), b->c64_tt_ck,
-                                     b->d_c64tab_ck[variant], b->d_c64part,
-                                     isal_hip_crc64_init_term(variant, b->len, init),
-                                     (uint64_t *) crc, stream)
-                       ? ISAL_HIP_EHIP
-                       : ISAL_HIP_OK;
-}
-
-static int
-batch_encode_crc64_impl(isal_hip_batch *b, int variant, unsigned long long init,
-                            unsigned long long *crc, void *stream)
-{
-        int r;
-        isal_hip_crc64_geom g;
-        if (!b || !crc || variant < 0 || variant >= ISAL_HIP_CRC64_NVARIANTS)
-                return ISAL_HIP_EINVAL;
-        if ((r = batch_crc64_setup(b, variant, 0)) != ISAL_HIP_OK)
-                return r;
-        isal_hip_crc64_geometry(b->len, b->c64_tt, &g);
-        if (b->vec16 && b->len % 16 == 0 && g.nblk > 0 && b->rows <= EC_MAX_ROWS_PER_PASS &&
-            b->k >= 1 && b->k <= ISAL_HIP_CRC64_MAX_FUSED_K)
-                /* one pass over the stripe: encode + CRC64 of all k + rows shards */
-                return isal_hip_launch_encode_crc64(
-                               b->d_ptrs, b->k, b->rows, b->nstripes, b->len, b->d_tbl, &b->xr,
-                               isal_hip_crc64_is_refl(variant), b->c64_tt, b->d_c64tab[variant],
-                               b->d_c64part, isal_hip_crc64_init_term(variant, b->len, init),
-                               (uint64_t *) crc, stream)
-                       ? ISAL_HIP_EHIP
-                       : ISAL_HIP_OK;
-        /* unaligned shards, short or ragged len, wide stripes: encode, then CRC64 */
-        if (isal_hip_batch_encode(b, stream) != ISAL_HIP_OK)
-                return ISAL_HIP_EHIP;
-        return isal_hip_batch_crc64(b, variant, init, crc, stream);
-}
-
-static int
-batch_encode_crc_impl(isal_hip_batch *b, unsigned int init, unsigned int *crc, void *stream)
-{
-        int r;
-        if (!b || !crc)
-                return ISAL_HIP_EINVAL;
-        if (b->len == 0)
-                return batch_crc_empty(b, init, crc, stream);
-        if ((r = batch_crc_setup(b)) != ISAL_HIP_OK)
-                return r;
-        if (b->vec16 && b->len % 16 == 0 && b->k >= 1 && b->k <= ISAL_HIP_CRC_MAX_FUSED_K) {
-                /* one pass over the stripe: encode + CRC of all k + rows shards
-                 * (row 0's chains formed from the sources' when it is a 0/1 row) */
-                if (isal_hip_launch_encode_crc(b->d_ptrs, b->k + b->rows, 0, b->k, b->d_tbl, &b->xr,
-                                               b->len, b->k, b->rows, b->nstripes, b->crc.tt,
-                                               b->d_crc, b->d_part, b->d_tail, stream))
-                        return ISAL_HIP_EHIP;
-        } else {
-                /* unaligned shards, ragged len or very wide k: encode, then CRC */
-                if (isal_hip_batch_encode(b, stream) != ISAL_HIP_OK)
-                        return ISAL_HIP_EHIP;
-                if (isal_hip_launch_crc(b->d_ptrs, b->k + b->rows, 0, b->k + b->rows, b->nstripes,
-                                        b->len, b->vec16, b->crc.tt, b->d_crc, b->d_part,
-                                        b->d_tail, b->k + b->rows, 0, stream))
-                        return ISAL_HIP_EHIP;
-        }
-        return batch_crc_finish(b, init, crc, stream);
-}
-
 /* ---- checksum entry points (crc.h, crc64.h) --------------------------------
  * The reference's crc32_iscsi (include/crc.h:136-150) and crc64_* flavours
  * (include/crc64.h:54-163, isa-l.def:75-122), routed like ec_encode_data: a
@@ -2561,8 +2057,6 @@ batch_encode_crc_impl(isal_hip_batch *b, unsigned int init, unsigned int *crc, v
  * last length (they depend on it); a storage caller checksums fragment after
  * fragment of one length. A failing HIP call on a device buffer aborts (no
  * CPU route can read it), as for the erasure-code calls. */
-
-static int crc_tiles(int len, int nstripes, int def);
 
 static hipError_t
 ensure_cpart(ctx_t *c, size_t bytes)
@@ -2611,7 +2105,7 @@ crc_device(const void *buf, uint64_t len)
 static uint64_t
 gpu_crc64_piece(const char *fn, int dev, int variant, uint64_t init, const unsigned char *buf, int len)
 {
-        const int tt = crc_tiles(len, 1, 64);
+        const int tt = isal_hip_crc_tiles(len, 1, 64);
         isal_hip_crc64_geom g;
         struct crcc *cc;
         hipError_t err = hipSuccess;
@@ -2745,14 +2239,12 @@ crc64_route(const char *fn, int variant, uint64_t init, const unsigned char *buf
 static uint32_t
 gpu_crc32c(const char *fn, int dev, uint32_t init, const unsigned char *buf, int len)
 {
-        const int tt = crc_tiles(len, 1, 64);
+        const int tt = isal_hip_crc_tiles(len, 1, 64);
         isal_hip_crc_geom g;
         struct crcc *cc;
         hipError_t err = hipSuccess;
         const char *what = NULL;
-        const size_t tab = ISAL_HIP_CRC_TAB_DWORDS,
-                     plan = ISAL_HIP_CRC_PLAN_DWORDS + ISAL_HIP_CRC_EXT_DWORDS + ISAL_HIP_CRC_B16_DWORDS +
-                            ISAL_HIP_CRC_FPRE_DWORDS;
+        const size_t tab = ISAL_HIP_CRC_TAB_DWORDS, image = (size_t) ISAL_HIP_CRC_IMAGE_DWORDS * 4;
         size_t part;
         ctx_t *c;
         uint32_t *h;
@@ -2764,26 +2256,24 @@ gpu_crc32c(const char *fn, int dev, uint32_t init, const unsigned char *buf, int
         cc = &c->c32;
         isal_hip_crc_geometry(len, tt, &g);
         if (!cc->d_tabs || cc->len != len || cc->tt != tt) {
-                /* all tables once, then per length only the combine plan */
+                /* the whole image once, then per length only the part that
+                 * depends on it (the combine plan) */
                 const int full = !cc->d_tabs || cc->len < 0;
-                uint32_t *t = (uint32_t *) malloc((tab + plan) * 4);
+                uint32_t *t = (uint32_t *) malloc(image);
                 if (!t) {
                         fprintf(stderr, "isal_hip: out of host memory\n");
                         abort();
                 }
-                isal_hip_crc32c_plan(len, tt, t + tab);
-                if (full) {
-                        isal_hip_crc32c_tables(t);
-                        isal_hip_crc32c_ext_tables(t, t + ISAL_HIP_CRC_EXT_TAB);
-                        isal_hip_crc32c_byte_tables(t + ISAL_HIP_CRC_B16_TAB);
-                        isal_hip_crc32c_pre_tables(t, t + ISAL_HIP_CRC_FPRE_TAB);
-                }
+                if (full)
+                        isal_hip_crc32c_image(len, tt, t);
+                else
+                        isal_hip_crc32c_image_len(len, tt, t);
                 cc->len = -1;
                 if (!cc->d_tabs)
-                        CRC_GPU_TRY(fn, "hipMalloc (checksum tables)", hipMalloc(&cc->d_tabs, (tab + plan) * 4));
+                        CRC_GPU_TRY(fn, "hipMalloc (checksum tables)", hipMalloc(&cc->d_tabs, image));
                 if (full)
                         CRC_GPU_TRY(fn, "hipMemcpy (checksum tables)",
-                                    hipMemcpy(cc->d_tabs, t, (tab + plan) * 4, hipMemcpyHostToDevice));
+                                    hipMemcpy(cc->d_tabs, t, image, hipMemcpyHostToDevice));
                 else
                         CRC_GPU_TRY(fn, "hipMemcpy (checksum tables)",
                                     hipMemcpy((uint32_t *) cc->d_tabs + tab, t + tab, ISAL_HIP_CRC_PLAN_DWORDS * 4,
@@ -2874,111 +2364,3 @@ CRC64_ENTRY(crc64_jones_norm, ISAL_HIP_CRC64_JONES_NORM)
 CRC64_ENTRY(crc64_rocksoft_refl, ISAL_HIP_CRC64_ROCKSOFT_REFL)
 CRC64_ENTRY(crc64_rocksoft_norm, ISAL_HIP_CRC64_ROCKSOFT_NORM)
 #undef CRC64_ENTRY
-
-/* ---- the batch entry points run on the batch's device -------------------- */
-
-int
-isal_hip_batch_set_tables(isal_hip_batch *b, const unsigned char *gftbls)
-{
-        int prev, r;
-        if (!b)
-                return ISAL_HIP_EINVAL;
-        if ((prev = isal_hip_dev_enter(b->device)) == -2)
-                return ISAL_HIP_EHIP;
-        r = batch_set_tables_impl(b, gftbls);
-        isal_hip_dev_leave(prev);
-        return r;
-}
-
-int
-isal_hip_batch_encode(isal_hip_batch *b, void *stream)
-{
-        int prev, r;
-        if (!b)
-                return ISAL_HIP_EINVAL;
-        if ((prev = isal_hip_dev_enter(b->device)) == -2)
-                return ISAL_HIP_EHIP;
-        r = batch_encode_impl(b, stream);
-        isal_hip_dev_leave(prev);
-        return r;
-}
-
-int
-isal_hip_batch_update(isal_hip_batch *b, int vec_i, void *stream)
-{
-        int prev, r;
-        if (!b)
-                return ISAL_HIP_EINVAL;
-        if ((prev = isal_hip_dev_enter(b->device)) == -2)
-                return ISAL_HIP_EHIP;
-        r = batch_update_impl(b, vec_i, stream);
-        isal_hip_dev_leave(prev);
-        return r;
-}
-
-int
-isal_hip_batch_check(isal_hip_batch *b, unsigned long long *bad, void *stream)
-{
-        int prev, r;
-        if (!b)
-                return ISAL_HIP_EINVAL;
-        if ((prev = isal_hip_dev_enter(b->device)) == -2)
-                return ISAL_HIP_EHIP;
-        r = batch_check_impl(b, bad, stream);
-        isal_hip_dev_leave(prev);
-        return r;
-}
-
-int
-isal_hip_batch_crc(isal_hip_batch *b, unsigned int init, unsigned int *crc, void *stream)
-{
-        int prev, r;
-        if (!b)
-                return ISAL_HIP_EINVAL;
-        if ((prev = isal_hip_dev_enter(b->device)) == -2)
-                return ISAL_HIP_EHIP;
-        r = batch_crc_impl(b, init, crc, stream);
-        isal_hip_dev_leave(prev);
-        return r;
-}
-
-int
-isal_hip_batch_crc64(isal_hip_batch *b, int variant, unsigned long long init,
-                     unsigned long long *crc, void *stream)
-{
-        int prev, r;
-        if (!b)
-                return ISAL_HIP_EINVAL;
-        if ((prev = isal_hip_dev_enter(b->device)) == -2)
-                return ISAL_HIP_EHIP;
-        r = batch_crc64_impl(b, variant, init, crc, stream);
-        isal_hip_dev_leave(prev);
-        return r;
-}
-
-int
-isal_hip_batch_encode_crc64(isal_hip_batch *b, int variant, unsigned long long init,
-                            unsigned long long *crc, void *stream)
-{
-        int prev, r;
-        if (!b)
-                return ISAL_HIP_EINVAL;
-        if ((prev = isal_hip_dev_enter(b->device)) == -2)
-                return ISAL_HIP_EHIP;
-        r = batch_encode_crc64_impl(b, variant, init, crc, stream);
-        isal_hip_dev_leave(prev);
-        return r;
-}
-
-int
-isal_hip_batch_encode_crc(isal_hip_batch *b, unsigned int init, unsigned int *crc, void *stream)
-{
-        int prev, r;
-        if (!b)
-                return ISAL_HIP_EINVAL;
-        if ((prev = isal_hip_dev_enter(b->device)) == -2)
-                return ISAL_HIP_EHIP;
-        r = batch_encode_crc_impl(b, init, crc, stream);
-        isal_hip_dev_leave(prev);
-        return r;
-}

@@ -5,7 +5,8 @@
  * its byte table is the reference), every lane of one block chained
  *   b' = P'(w0 ^ b, w1, w2, w3)  (last tile: P)   and   b' = F'(...)  (last: F),
  * lanes joined with x^(8 * 16 * (255 - L)) and compared with the bytewise CRC
- * of the whole block. Test infrastructure only.
+ * of the whole block; then the layout of the whole device image
+ * (image_check). Test infrastructure only.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -32,6 +33,80 @@ fields32(const uint32_t *t, const uint32_t w[4])
                         r ^= t[(d * ISAL_HIP_CRC_FIELDS + f) * 32 +
                                ((w[d] >> field_lo(f)) & ((1u << field_bits(f)) - 1))];
         return r;
+}
+
+/* The device image (isal_hip_crc32c_image): every sub-table at its macro
+ * offset equals what its own builder produces, the image is exactly
+ * ISAL_HIP_CRC_IMAGE_DWORDS long (guard words after it stay untouched), and
+ * isal_hip_crc32c_image_len of another geometry written over an image yields
+ * that geometry's image word for word — what the drop-in checksum route relies
+ * on when the length changes (a plan that overlapped B16 or F' would show). */
+#define GUARD_WORDS 64
+#define GUARD 0xA5C3F00Du
+
+static uint32_t *
+image_of(long long len, int tt)
+{
+        uint32_t *im = malloc(4 * (ISAL_HIP_CRC_IMAGE_DWORDS + GUARD_WORDS));
+        int i;
+        for (i = 0; i < ISAL_HIP_CRC_IMAGE_DWORDS + GUARD_WORDS; i++)
+                im[i] = GUARD;
+        isal_hip_crc32c_image(len, tt, im);
+        return im;
+}
+
+static int
+same(const char *what, const uint32_t *got, const uint32_t *want, size_t n)
+{
+        if (!memcmp(got, want, 4 * n))
+                return 0;
+        printf("image: %s differs\n", what);
+        return 1;
+}
+
+static int
+image_check(void)
+{
+        static const struct {
+                long long len;
+                int tt;
+        } geo[2] = { { 3 * ISAL_HIP_CRC_TILE, 2 }, { 5 * ISAL_HIP_CRC_TILE + 19, 4 } };
+        uint32_t *im[2], *part = malloc(4 * ISAL_HIP_CRC_IMAGE_DWORDS);
+        int g, i, bad = 0;
+        for (g = 0; g < 2; g++) {
+                im[g] = image_of(geo[g].len, geo[g].tt);
+                isal_hip_crc32c_tables(part);
+                bad |= same("base tables", im[g], part, ISAL_HIP_CRC_TAB_DWORDS);
+                isal_hip_crc32c_pre_tables(part, part + ISAL_HIP_CRC_TAB_DWORDS);
+                bad |= same("F'", im[g] + ISAL_HIP_CRC_FPRE_TAB, part + ISAL_HIP_CRC_TAB_DWORDS,
+                            ISAL_HIP_CRC_FPRE_DWORDS);
+                isal_hip_crc32c_plan(geo[g].len, geo[g].tt, part);
+                bad |= same("plan", im[g] + ISAL_HIP_CRC_TAB_DWORDS, part, ISAL_HIP_CRC_PLAN_DWORDS);
+                isal_hip_crc32c_byte_tables(part);
+                bad |= same("B16", im[g] + ISAL_HIP_CRC_B16_TAB, part, ISAL_HIP_CRC_B16_DWORDS);
+                if (ISAL_HIP_CRC_B16_TAB != ISAL_HIP_CRC_TAB_DWORDS + ISAL_HIP_CRC_PLAN_DWORDS ||
+                    ISAL_HIP_CRC_FPRE_TAB != ISAL_HIP_CRC_B16_TAB + ISAL_HIP_CRC_B16_DWORDS ||
+                    ISAL_HIP_CRC_IMAGE_DWORDS != ISAL_HIP_CRC_FPRE_TAB + ISAL_HIP_CRC_FPRE_DWORDS) {
+                        printf("image: the sub-tables do not tile the image\n");
+                        bad = 1;
+                }
+                for (i = 0; i < GUARD_WORDS; i++)
+                        if (im[g][ISAL_HIP_CRC_IMAGE_DWORDS + i] != GUARD) {
+                                printf("image: guard word %d overwritten\n", i);
+                                bad = 1;
+                        }
+        }
+        if (!memcmp(im[0], im[1], 4 * ISAL_HIP_CRC_IMAGE_DWORDS)) {
+                printf("image: the two geometries do not differ\n");
+                bad = 1;
+        }
+        isal_hip_crc32c_image_len(geo[1].len, geo[1].tt, im[0]);
+        bad |= same("image_len over another geometry's image", im[0], im[1],
+                    ISAL_HIP_CRC_IMAGE_DWORDS + GUARD_WORDS);
+        free(im[0]);
+        free(im[1]);
+        free(part);
+        return bad;
 }
 
 int
@@ -72,7 +147,11 @@ main(void)
                 printf("byte path %08x field path %08x want %08x\nFAIL\n", x_b, x_f, want);
                 return 1;
         }
-        printf("crc32c chain algebra ok (byte-position and field paths)\n");
+        if (image_check()) {
+                printf("FAIL\n");
+                return 1;
+        }
+        printf("crc32c chain algebra ok (byte-position and field paths); device image ok\n");
         free(buf);
         free(tabs);
         free(pos);

@@ -35,6 +35,34 @@ fields(const uint64_t *t, const uint32_t w[4])
         return r;
 }
 
+/* isal_hip_crc64_len_tables of geometry B written over the table set of
+ * geometry A yields the table set of B word for word: what the drop-in
+ * checksum route relies on when the length changes. */
+static int
+len_tables_check(int variant)
+{
+        const long long len_a = 3 * ISAL_HIP_CRC_TILE, len_b = 5 * ISAL_HIP_CRC_TILE + 19;
+        const int tt_a = 2, tt_b = 4;
+        const size_t bytes = sizeof(uint64_t) * ISAL_HIP_CRC64_TAB_ENTRIES;
+        uint64_t *a = malloc(bytes), *b = malloc(bytes);
+        int bad = 0;
+        isal_hip_crc64_tables(variant, len_a, tt_a, a);
+        isal_hip_crc64_tables(variant, len_b, tt_b, b);
+        if (!memcmp(a, b, bytes)) {
+                printf("variant %d: the two geometries' tables do not differ\n", variant);
+                bad = 1;
+        }
+        isal_hip_crc64_len_tables(variant, len_b, tt_b, a);
+        if (memcmp(a, b, bytes)) {
+                printf("variant %d: len_tables over another geometry's tables differ from a fresh set\n",
+                       variant);
+                bad = 1;
+        }
+        free(a);
+        free(b);
+        return bad;
+}
+
 int
 main(void)
 {
@@ -80,7 +108,22 @@ main(void)
                         }
                 }
         }
-        printf(bad ? "FAIL\n" : "crc64 chain algebra ok (8 flavours, slicing and field paths)\n");
+        /* the first refl and the first norm flavour */
+        {
+                int done[2] = { 0, 0 };
+                for (variant = 0; variant < 8; variant++) {
+                        const int r = isal_hip_crc64_is_refl(variant) != 0;
+                        if (!done[r]) {
+                                done[r] = 1;
+                                bad |= len_tables_check(variant);
+                        }
+                }
+                if (!done[0] || !done[1]) {
+                        printf("len tables: no refl or no norm flavour found\n");
+                        bad = 1;
+                }
+        }
+        printf(bad ? "FAIL\n" : "crc64 chain algebra ok (8 flavours, slicing and field paths); len tables ok\n");
         free(buf);
         free(tabs);
         return bad;

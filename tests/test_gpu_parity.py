@@ -2376,6 +2376,32 @@ def test_crc_entry_points_device_buffers_vs_oracle(engine, oracle, gpu):
     assert engine.kernel_launches() > launches, "the GPU checksum kernels did not run"
 
 
+def test_crc_entry_points_changing_length_reuploads_only_the_length_tables(engine, oracle, gpu):
+    """One 16-byte aligned device buffer checksummed at a changing length: each
+    change re-uploads only the length-dependent tables (the CRC32C combine
+    plan; CRC64 OP_BLOCK / OP_LAST / OP_TAIL) over the thread's device copy.
+    Aligned lengths with at least two full tiles make the *_shards_pre kernels
+    read F' (behind the plan in the CRC32C image) for every tile but the last,
+    so a partial upload that reached past its part shows: == the oracle at
+    every length, non-zero inits."""
+    import torch
+
+    lengths = [3 * 4096, 5 * 4096 + 16 + 3, 3 * 4096, 2 * 4096 + 8]
+    host = fill_bytes(max(lengths), 9091)
+    dev = torch.from_numpy(host).to(gpu)
+    p = dev.data_ptr()
+    assert p % 16 == 0
+    variants = [engine.CRC64_VARIANTS.index("ecma_refl"), engine.CRC64_VARIANTS.index("ecma_norm")]
+    launches = engine.kernel_launches()
+    for n in lengths:
+        i32 = 0x9E3779B9 ^ n
+        assert engine.crc32_iscsi(p, n, i32) == oracle.crc32_iscsi(host[:n], i32), ("crc32_iscsi", n)
+        for v in variants:
+            i64 = 0x0123456789ABCDEF + 4 * n + v
+            assert engine.crc64(v, i64, p, n) == oracle.crc64(v, host[:n], i64), (engine.CRC64_VARIANTS[v], n)
+    assert engine.kernel_launches() > launches, "the GPU checksum kernels did not run"
+
+
 def test_crc_entry_points_host_buffers_staged_under_gpu_backend(engine, oracle, gpu):
     """Under ISAL_HIP_BACKEND=gpu (this module's setting) host buffers are staged
     into HBM and checksummed by the kernels too: == the oracle."""
