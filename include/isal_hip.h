@@ -27,6 +27,7 @@ extern "C" {
 #define ISAL_HIP_EHIP (-2)     /* a HIP runtime call failed */
 #define ISAL_HIP_ENOMEM (-3)   /* host or device allocation failed */
 #define ISAL_HIP_EDEVICE (-4)  /* a shard pointer is on another GPU than the object's device */
+#define ISAL_HIP_ESINGULAR (-5) /* an erasure pattern's survivor matrix is not invertible */
 
 typedef struct isal_hip_batch isal_hip_batch;
 
@@ -118,6 +119,63 @@ int isal_hip_batch_crc64(isal_hip_batch *b, int variant, unsigned long long init
  * k <= 32 (otherwise encode, then isal_hip_batch_crc64). */
 int isal_hip_batch_encode_crc64(isal_hip_batch *b, int variant, unsigned long long init,
                                 unsigned long long *crc, void *stream);
+
+/* ---- repair batch: mixed erasure patterns in one launch ------------------ */
+
+/*
+ * The recovery rows for one erasure pattern: pure host arithmetic, no GPU.
+ * a: the m*k encode matrix (gf_gen_rs_matrix / gf_gen_cauchy1_matrix layout,
+ *    identity on top), m <= 256.
+ * errs: nerrs distinct shard indices in [0, m), any order, 1 <= nerrs <= m - k.
+ * survivors[k]: the first k non-erased indices, ascending.
+ * c[nerrs*k]: row i rebuilds shard errs[i] from those survivors: the
+ *    survivors' rows of a are inverted; a data shard takes its row of the
+ *    inverse, a parity shard its encode row times the inverse.
+ * ISAL_HIP_ESINGULAR when the survivors' rows are not invertible,
+ * ISAL_HIP_EINVAL for arguments outside the contract.
+ */
+int isal_hip_decode_matrix(int k, int m, const unsigned char *a, int nerrs,
+                           const unsigned char *errs, unsigned char *c, unsigned char *survivors);
+
+/*
+ * A rebuild after device loss: placement rotates shards over devices, so the
+ * lost device is another shard index in every stripe. A repair batch covers
+ * nstripes stripes of one geometry (len bytes per shard, k of m shards
+ * suffice), each with its OWN set of nerrs erased shards, and rebuilds all
+ * of them with one kernel launch per pass of isal_hip_max_rows_per_pass()
+ * rows, on the caller's stream.
+ *   shards: host array of nstripes*m DEVICE pointers, shards[s*m + i] = shard
+ *           i of stripe s. A stripe's erased entries are its destinations;
+ *           its first k others (ascending) are read, nothing else is touched.
+ *   errs:   nstripes*nerrs shard indices, errs[s*nerrs + i] for stripe s
+ *           (in range, distinct within the stripe, any order).
+ * Every entry of shards must be non-NULL and 16-byte aligned
+ * (ISAL_HIP_EINVAL); memory kinds and device ownership as for
+ * isal_hip_batch_create. Any len >= 0 is valid. A stripe whose pattern is not
+ * decodable fails the whole create with ISAL_HIP_ESINGULAR and nothing is
+ * launched; *bad_stripe (optional) then names the first such stripe, as it
+ * does the first stripe with a bad index or pointer on ISAL_HIP_EINVAL (-1
+ * otherwise). All of these checks run before the first HIP call, so they
+ * answer the same on a host without a GPU.
+ * create derives the recovery rows of every distinct pattern and uploads
+ * pointer and coefficient tables once; isal_hip_repair_run only enqueues
+ * kernels, may be called repeatedly and is idempotent. The coefficient
+ * tables take 20*k*nerrs bytes per distinct pattern; more than
+ * ISAL_HIP_REPAIR_MAX_TABLE_BYTES of them (over 100000 patterns of a k = 10,
+ * nerrs = 3 layout; far past the few MiB of L2 that let neighbouring
+ * workgroups share a pattern's tables) is refused with ISAL_HIP_ENOMEM.
+ * Out of scope: erasure counts that differ within one object (one object per
+ * count), unaligned or host-pageable shards, and any CPU route.
+ */
+#define ISAL_HIP_REPAIR_MAX_TABLE_BYTES (64u << 20)
+typedef struct isal_hip_repair isal_hip_repair;
+int isal_hip_repair_create(isal_hip_repair **out, int len, int k, int m, const unsigned char *a,
+                           int nerrs, int nstripes, const unsigned char *errs,
+                           unsigned char *const *shards, int *bad_stripe);
+int isal_hip_repair_run(isal_hip_repair *r, void *stream);
+/* distinct erasure patterns found by create */
+int isal_hip_repair_npatterns(const isal_hip_repair *r);
+int isal_hip_repair_destroy(isal_hip_repair *r);
 
 /* ---- streaming pipeline for HOST-resident stripes ----------------------- */
 

@@ -1017,6 +1017,71 @@ unsigned stripes_per_launch(int len, bool vec16, long long vspan = kTile) {
   return static_cast<unsigned>(n > 0 ? n : 1);
 }
 
+// ---------------------------------------------------------------------------
+// Repair: the vector encode with one coefficient table per erasure pattern
+// (isal_hip_repair.c, DESIGN §3 "Repair batch"). Row r of the pointer table
+// (k survivors, then P destinations) rebuilds its stripe with pattern pat[r]'s
+// tables, at tbl0 + pat[r] * tbl_stride (tbl0 already points at the pass).
+// The row index comes from blockIdx, so pat[r] and the table address are
+// wave-uniform: the index is a scalar load, readfirstlane pins the address to
+// SGPRs, and the coefficients stay scalar loads exactly as in ec_encode_v16.
+// Always the plain lookup form (kEncLUT): the 0/1 masks of kEncXor belong to
+// one matrix, not to a mix of patterns.
+// ---------------------------------------------------------------------------
+template <int P, class Pol, int B>
+__global__ __launch_bounds__(B, (enc_waves<P, Pol::U, kEncLUT>())) void ec_repair_v16(
+    const uint64_t* __restrict__ ptrs, int ptr_stride, const uint32_t* __restrict__ pat,
+    const uint32_t* __restrict__ tbl0, unsigned tbl_stride, int dst0, int len, int k, unsigned nitems,
+    unsigned tiles) {
+  for (unsigned w = blockIdx.x; w < nitems; w += gridDim.x) {
+    unsigned row, tile;
+    EncOrder<Pol::ORDER>::item(w, nitems, tiles, row, tile);
+    const uint64_t* __restrict__ sp = ptrs + static_cast<size_t>(row) * ptr_stride;
+    const unsigned p = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(pat[row])));
+    const uint32_t* __restrict__ tbl = tbl0 + static_cast<size_t>(p) * tbl_stride;
+    const long long off = static_cast<long long>(tile) * (B * kVec) + threadIdx.x * kVec;
+    if (off + kVec <= len) {
+      uint32_t acc[P][4];
+      accum16<P, Pol, kEncLUT>(acc, sp, tbl, k, off, len);
+#pragma unroll
+      for (int l = 0; l < P; ++l)
+        store16<Pol::ST>(sp[dst0 + l], off, make_uint4(acc[l][0], acc[l][1], acc[l][2], acc[l][3]), len);
+    } else if (off < len) {
+      dot_bytes<P>(sp, 0, dst0, tbl, k, off, static_cast<int>(len - off));
+    }
+  }
+}
+
+// One pass of P rows over nrows table rows: block shape, occupancy cap, work
+// order and load group are the vector encode's (enc_block, enc_lds_alloc,
+// order 2, enc_group).
+template <int P, int U>
+void launch_repair(hipStream_t s, const uint64_t* ptrs, int ptr_stride, const uint32_t* pat, const uint32_t* tbl0,
+                   unsigned tbl_stride, int dst0, int len, int k, unsigned nrows) {
+  constexpr int B = enc_block<P>();
+  if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2) fprintf(stderr, "isal_hip: kernel ec_repair_v16<%d, %d, %d>\n", P, U, B);
+  const unsigned tiles = static_cast<unsigned>((static_cast<long long>(len) + B * kVec - 1) / (B * kVec));
+  const unsigned nitems = nrows * tiles;
+  ISAL_LAUNCH((ec_repair_v16<P, EncPol<U, kBufNT, kBufNT, 2>, B>), dim3(grid_for(nitems)), dim3(B),
+              enc_lds_alloc(0, P), s, ptrs, ptr_stride, pat, tbl0, tbl_stride, dst0, len, k, nitems, tiles);
+}
+
+template <int P>
+hipError_t repair_pass(hipStream_t s, const uint64_t* ptrs, int ptr_stride, const uint32_t* pat, const uint32_t* tbl0,
+                       unsigned tbl_stride, int dst0, int len, int k, unsigned nrows) {
+  switch (enc_group(k, P)) {
+#define EC_GROUP(u)                                                                          \
+  case u:                                                                                    \
+    launch_repair<P, u>(s, ptrs, ptr_stride, pat, tbl0, tbl_stride, dst0, len, k, nrows);   \
+    break;
+    EC_GROUP(12) EC_GROUP(10) EC_GROUP(8) EC_GROUP(6) EC_GROUP(5)
+#undef EC_GROUP
+    default: launch_repair<P, 4>(s, ptrs, ptr_stride, pat, tbl0, tbl_stride, dst0, len, k, nrows); break;
+  }
+  isal_hip_count_launch();
+  return hipGetLastError();
+}
+
 }  // namespace
 
 // The 0/1 masks of a call, or none under ISAL_HIP_ENC_XOR=0 (read at launch,
@@ -1052,6 +1117,33 @@ extern "C" int isal_hip_launch_encode(const uint64_t* d_ptrs, int ptr_stride, in
 #define EC_CASE(n)                                                                                      \
   case n:                                                                                               \
     e = encode_pass<n>(ptrs, ptr_stride, src_idx0, dst0, tbl, ldsx, len, k, ns, vec16 != 0, x, r0m, c0m, s); \
+    break;
+        EC_CASE(1) EC_CASE(2) EC_CASE(3) EC_CASE(4) EC_CASE(5) EC_CASE(6) EC_CASE(7) EC_CASE(8)
+#undef EC_CASE
+      }
+      if (e != hipSuccess) return static_cast<int>(e);
+    }
+  }
+  return 0;
+}
+
+extern "C" int isal_hip_launch_repair(const uint64_t* d_ptrs, int ptr_stride, const uint32_t* d_pat,
+                                      const uint32_t* d_tbl, unsigned tbl_stride, int len, int k, int rows,
+                                      long long nrows, void* stream) {
+  if (len <= 0 || rows <= 0 || nrows <= 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned per = stripes_per_launch(len, true, kEncMinSpan);
+  for (long long s0 = 0; s0 < nrows; s0 += per) {
+    const unsigned ns = static_cast<unsigned>(nrows - s0 < per ? nrows - s0 : per);
+    const uint64_t* ptrs = d_ptrs + s0 * ptr_stride;
+    for (int r0 = 0; r0 < rows; r0 += EC_MAX_ROWS_PER_PASS) {
+      const int P = rows - r0 < EC_MAX_ROWS_PER_PASS ? rows - r0 : EC_MAX_ROWS_PER_PASS;
+      const uint32_t* tbl0 = d_tbl + static_cast<size_t>(kTbl) * k * r0;
+      hipError_t e = hipSuccess;
+      switch (P) {
+#define EC_CASE(n)                                                                                   \
+  case n:                                                                                            \
+    e = repair_pass<n>(s, ptrs, ptr_stride, d_pat + s0, tbl0, tbl_stride, k + r0, len, k, ns);       \
     break;
         EC_CASE(1) EC_CASE(2) EC_CASE(3) EC_CASE(4) EC_CASE(5) EC_CASE(6) EC_CASE(7) EC_CASE(8)
 #undef EC_CASE

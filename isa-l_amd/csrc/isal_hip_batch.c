@@ -5,7 +5,7 @@
  * alone or fused with the encode (crc_kernels.hip, crc64_kernels.hip).
  *
  * A batch belongs to the device that was current when it was created; every
- * entry point runs on that device (ON_BATCH_DEVICE below).
+ * entry point runs on that device (ON_BATCH_DEVICE, isal_hip_internal.h).
  */
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -39,8 +39,8 @@ struct isal_hip_batch {
  * memory, or page-locked host memory whose device address is its host address.
  * A stripe's shards usually come from a few allocations, so a device range
  * already seen answers without a HIP query. */
-static int
-batch_check_ptrs(const uint64_t *ptrs, size_t n, size_t len, int dev)
+int
+isal_hip_batch_check_ptrs(const uint64_t *ptrs, size_t n, size_t len, int dev)
 {
         seen_t sn;
         size_t i;
@@ -119,7 +119,7 @@ isal_hip_batch_create(isal_hip_batch **out, int len, int k, int rows, const unsi
                 isal_hip_batch_destroy(b);
                 return ISAL_HIP_EHIP;
         }
-        if (len > 0 && (j = batch_check_ptrs(h_ptrs, nptr, (size_t) len, b->device)) != ISAL_HIP_OK) {
+        if (len > 0 && (j = isal_hip_batch_check_ptrs(h_ptrs, nptr, (size_t) len, b->device)) != ISAL_HIP_OK) {
                 free(h_ptrs);
                 isal_hip_batch_destroy(b);
                 return j;
@@ -479,19 +479,8 @@ batch_encode_crc_impl(isal_hip_batch *b, unsigned int init, unsigned int *crc, v
         return batch_crc_finish(b, init, crc, stream);
 }
 
-/* ---- the batch entry points run on the batch's device -------------------- */
-
-#define ON_BATCH_DEVICE(b, call)                                                                   \
-        do {                                                                                       \
-                int prev_, r_;                                                                     \
-                if (!(b))                                                                          \
-                        return ISAL_HIP_EINVAL;                                                    \
-                if ((prev_ = isal_hip_dev_enter((b)->device)) == -2)                               \
-                        return ISAL_HIP_EHIP;                                                      \
-                r_ = (call);                                                                       \
-                isal_hip_dev_leave(prev_);                                                         \
-                return r_;                                                                         \
-        } while (0)
+/* ---- the batch entry points run on the batch's device (ON_BATCH_DEVICE,
+ * isal_hip_internal.h) ---------------------------------------------------- */
 
 int
 isal_hip_batch_set_tables(isal_hip_batch *b, const unsigned char *gftbls)

@@ -219,6 +219,35 @@ seen_add(seen_t *sn, uintptr_t base, size_t size, int dev)
 int isal_hip_dev_enter(int dev);
 void isal_hip_dev_leave(int prev);
 
+/* Body of an entry point on an object b that belongs to b->device (a batch,
+ * a repair batch): run call there, whatever the thread's current device. */
+#define ON_BATCH_DEVICE(b, call)                                                                   \
+        do {                                                                                       \
+                int prev_, r_;                                                                     \
+                if (!(b))                                                                          \
+                        return ISAL_HIP_EINVAL;                                                    \
+                if ((prev_ = isal_hip_dev_enter((b)->device)) == -2)                               \
+                        return ISAL_HIP_EHIP;                                                      \
+                r_ = (call);                                                                       \
+                isal_hip_dev_leave(prev_);                                                         \
+                return r_;                                                                         \
+        } while (0)
+
+/* Every one of the n shards [ptrs[i], ptrs[i] + len) reachable by a kernel on
+ * device dev: hipMalloc memory of dev, managed memory, or page-locked host
+ * memory mapped at its host address (isal_hip_batch.c). ISAL_HIP_OK,
+ * ISAL_HIP_EINVAL (NULL, pageable) or ISAL_HIP_EDEVICE (another GPU's). */
+int isal_hip_batch_check_ptrs(const uint64_t *ptrs, size_t n, size_t len, int dev);
+
+/* Repair (ec_kernels.hip ec_repair_v16): the vector encode over nrows rows of
+ * a pointer table (k survivors then rows destinations, stride ptr_stride,
+ * every shard 16-byte aligned) where row r takes the coefficient tables of
+ * pattern d_pat[r]: d_tbl + d_pat[r] * tbl_stride dwords, each pattern laid
+ * out like one encode's tables (passes of EC_MAX_ROWS_PER_PASS rows). */
+int isal_hip_launch_repair(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_pat,
+                           const uint32_t *d_tbl, unsigned tbl_stride, int len, int k, int rows,
+                           long long nrows, void *stream);
+
 /* Kernel registry (isal_hip_selftest_kernels): every kernel a launcher can
  * launch registers its host handle and a name when the library loads
  * (ec_device.h ISAL_LAUNCH). */

@@ -26,7 +26,7 @@ __all__ = [
     "gf_invert_matrix", "gf_vect_mul_init", "ec_init_tables", "ec_encode_data",
     "ec_encode_data_base", "ec_encode_data_update", "ec_encode_data_update_base",
     "gf_vect_dot_prod", "gf_vect_dot_prod_base", "gf_vect_mad", "gf_vect_mad_base",
-    "gf_vect_mul", "gf_vect_mul_base", "Batch", "Pipe", "kernel_launches", "max_rows_per_pass",
+    "gf_vect_mul", "gf_vect_mul_base", "Batch", "Repair", "decode_matrix", "ESINGULAR", "Pipe", "kernel_launches", "max_rows_per_pass",
     "version", "addr", "cpu_calls", "fallbacks", "reload_config", "Multi", "partition",
     "route_device", "contexts_created", "selftest_kernels", "crc32_iscsi", "crc64", "CRC64_VARIANTS", "slow_waits",
 ]
@@ -105,6 +105,12 @@ def lib() -> ctypes.CDLL:
             "isal_hip_batch_crc64": (i, [ctypes.c_void_p, i, ctypes.c_ulonglong, ctypes.c_void_p, ctypes.c_void_p]),
             "isal_hip_batch_encode_crc64": (i, [ctypes.c_void_p, i, ctypes.c_ulonglong, ctypes.c_void_p,
                                                 ctypes.c_void_p]),
+            "isal_hip_decode_matrix": (i, [i, i, _u8p, i, _u8p, _u8p, _u8p]),
+            "isal_hip_repair_create": (i, [ctypes.POINTER(ctypes.c_void_p), i, i, i, _u8p, i, i, _u8p, _u8pp,
+                                           ctypes.POINTER(ctypes.c_int)]),
+            "isal_hip_repair_run": (i, [ctypes.c_void_p, ctypes.c_void_p]),
+            "isal_hip_repair_npatterns": (i, [ctypes.c_void_p]),
+            "isal_hip_repair_destroy": (i, [ctypes.c_void_p]),
             "isal_hip_pipe_create": (i, [ctypes.POINTER(ctypes.c_void_p), i, i, i, _u8p, i, i]),
             "isal_hip_pipe_submit": (i, [ctypes.c_void_p, _u8pp, _u8pp]),
             "isal_hip_pipe_flush": (i, [ctypes.c_void_p]),
@@ -353,6 +359,65 @@ class Batch:
     def close(self) -> None:
         if getattr(self, "_h", None):
             lib().isal_hip_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+ESINGULAR = -5  # ISAL_HIP_ESINGULAR
+
+
+def decode_matrix(a, k: int, errs: Sequence[int]):
+    """isal_hip_decode_matrix (host arithmetic, no GPU): (ret, c, survivors) for
+    the m x k encode matrix a and the erased shard indices errs. c is
+    len(errs) x k, row i rebuilding shard errs[i] from the survivors (the first
+    k non-erased indices); ret is 0, ESINGULAR or -1 (bad arguments)."""
+    a = _u8(a)
+    m = a.size // k
+    e = np.array(list(errs), dtype=np.uint8)
+    c = np.zeros(max(1, e.size * k), dtype=np.uint8)
+    surv = np.zeros(max(1, k), dtype=np.uint8)
+    ret = lib().isal_hip_decode_matrix(k, m, _p(a), int(e.size), _p(e), _p(c), _p(surv))
+    return int(ret), c[:e.size * k], [int(x) for x in surv[:k]]
+
+
+class Repair:
+    """nstripes stripes of one geometry, each with its own nerrs erased shards,
+    rebuilt by one launch per pass (include/isal_hip.h repair batch).
+
+    shards[s*m + i] is the address (or tensor) of shard i of stripe s, every
+    one a 16-byte aligned device buffer; errs[s*nerrs + i] the erased indices
+    of stripe s. run() only enqueues on `stream` and may be repeated."""
+
+    def __init__(self, len_: int, k: int, m: int, a, nerrs: int, nstripes: int, errs: Sequence[int],
+                 shards: Sequence):
+        if len(errs) != nstripes * nerrs or len(shards) != nstripes * m:
+            raise ValueError("errs must hold nstripes*nerrs entries and shards nstripes*m")
+        e = np.array(list(errs), dtype=np.uint8)
+        h, bad = ctypes.c_void_p(), ctypes.c_int(-1)
+        rc = lib().isal_hip_repair_create(ctypes.byref(h), len_, k, m, _p(_u8(a)), nerrs, nstripes, _p(e),
+                                          _pp(shards), ctypes.byref(bad))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_repair_create failed ({rc}, stripe {bad.value})")
+        self.len, self.k, self.m, self.nerrs, self.nstripes = len_, k, m, nerrs, nstripes
+        self._h = h
+
+    def run(self, stream: int = 0) -> None:
+        rc = lib().isal_hip_repair_run(self._h, ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_repair_run failed ({rc})")
+
+    def npatterns(self) -> int:
+        """Distinct erasure patterns among the stripes."""
+        return int(lib().isal_hip_repair_npatterns(self._h))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().isal_hip_repair_destroy(self._h)
             self._h = None
 
     def __del__(self):
