@@ -51,8 +51,12 @@ int isal_hip_batch_create(isal_hip_batch **out, int len, int k, int rows,
                           unsigned char *const *coding);
 
 /* Replace the coefficient tables (e.g. a decode matrix) of an existing batch.
- * Synchronises the device first: launches already queued on any stream keep
- * the coefficients they were enqueued with. */
+ * Synchronises the device before the old tables go: launches already queued
+ * on any stream keep the coefficients they were enqueued with.
+ * All or nothing: everything derived from gftbls (coefficient tables, 0/1 row
+ * and column masks, derived-checksum rows, LDS product tables) is built and
+ * uploaded aside and published together; after a failure the batch still
+ * computes the old matrix in every entry point. */
 int isal_hip_batch_set_tables(isal_hip_batch *b, const unsigned char *gftbls);
 
 /* Enqueue ec_encode_data for every stripe of the batch on stream. */
@@ -66,8 +70,11 @@ int isal_hip_batch_update(isal_hip_batch *b, int vec_i, void *stream);
  * whole batch, e.g. a scrub): each stripe's coding rows are recomputed from
  * its sources and compared with the stored bytes; nothing is written to the
  * shards. bad: DEVICE array of nstripes words, bad[s] = ~0 when stripe s is
- * consistent, else its first mismatch as column << 8 | row (smallest column,
- * then row). Needs every shard 16-byte aligned (ISAL_HIP_EINVAL otherwise). */
+ * consistent, else its first mismatch as column << 8 | row: the smallest
+ * mismatching column of any row, then the smallest row at that column,
+ * whichever lane, workgroup or (rows > 8) pass found it. Every word of bad is
+ * rewritten by each call with len > 0. Needs every shard 16-byte aligned (ISAL_HIP_EINVAL
+ * otherwise, nothing enqueued). */
 int isal_hip_batch_check(isal_hip_batch *b, unsigned long long *bad, void *stream);
 
 int isal_hip_batch_destroy(isal_hip_batch *b);

@@ -139,11 +139,21 @@ isal_hip_batch_create(isal_hip_batch **out, int len, int k, int rows, const unsi
         return ISAL_HIP_OK;
 }
 
+/* The HIP call at an ISAL_HIP_FAULT site of the batch (isal_hip_internal.h):
+ * an armed site fails without the call being issued. */
+#define BATCH_TRY_AT(site, call) (isal_hip_knob(ISAL_HIP_KNOB_FAULT) == (site) ? hipErrorOutOfMemory : (call))
+
+/* All or nothing: the new coefficient tables, the LDS product tables of the
+ * wide passes and the host-side row masks are built and uploaded into fresh
+ * device buffers first; only when nothing can fail any more are they
+ * published together and the old buffers freed. A failed replacement leaves
+ * d_tbl, d_ldsx, xr and em on the old matrix, and the batch usable. */
 static int
 batch_set_tables_impl(isal_hip_batch *b, const unsigned char *gftbls)
 {
-        size_t n;
-        uint32_t *h;
+        size_t n, nw = 0;
+        uint32_t *h, *d_tbl = NULL;
+        uint64_t *hx = NULL, *d_ldsx = NULL;
         hipError_t e;
         isal_hip_xrows xr;
         isal_hip_encmask em;
@@ -153,40 +163,55 @@ batch_set_tables_impl(isal_hip_batch *b, const unsigned char *gftbls)
         h = (uint32_t *) malloc(n * 4 + 4);
         if (!h)
                 return ISAL_HIP_ENOMEM;
-        isal_hip_build_tables(b->k, b->rows, gftbls, h);
-        /* published with the device tables only: a failed update keeps the
-         * old row masks beside the old coefficients */
-        isal_hip_xor_rows(b->k, b->rows, gftbls, &xr);
-        isal_hip_enc_masks(b->k, b->rows, gftbls, &em);
-        if (!b->d_tbl) {
-                if (hipMalloc((void **) &b->d_tbl, n * 4 + 4) != hipSuccess) {
-                        free(h);
-                        return ISAL_HIP_EHIP;
-                }
-                e = hipSuccess;
-        } else {
-                /* launches already queued on any (possibly non-blocking) stream may
-                 * still read the old coefficients: let them finish first */
-                e = hipDeviceSynchronize();
-        }
-        if (e == hipSuccess)
-                e = hipMemcpy(b->d_tbl, h, n * 4, hipMemcpyHostToDevice);
-        free(h);
         /* the wide passes' LDS product tables (ec_encode_ldsx): k <= 64, a
          * pass of at least 4 rows (4 only when ISAL_HIP_ENC_LDSX=1 forces it) */
-        if (e == hipSuccess && b->k >= 1 && b->k <= 64 && b->rows >= 4) {
-                const size_t nw = isal_hip_ldsx_words(b->k, b->rows);
-                uint64_t *hx = (uint64_t *) malloc(nw * 8);
-                if (!hx)
+        if (b->k >= 1 && b->k <= 64 && b->rows >= 4) {
+                nw = isal_hip_ldsx_words(b->k, b->rows);
+                hx = (uint64_t *) malloc(nw * 8);
+                if (!hx) {
+                        free(h);
                         return ISAL_HIP_ENOMEM;
+                }
                 isal_hip_build_ldsx_tables(b->k, b->rows, gftbls, hx);
-                if (!b->d_ldsx && hipMalloc((void **) &b->d_ldsx, nw * 8) != hipSuccess)
-                        b->d_ldsx = NULL;
-                e = b->d_ldsx ? hipMemcpy(b->d_ldsx, hx, nw * 8, hipMemcpyHostToDevice) : hipSuccess;
-                free(hx);
         }
-        if (e != hipSuccess)
+        isal_hip_build_tables(b->k, b->rows, gftbls, h);
+        isal_hip_xor_rows(b->k, b->rows, gftbls, &xr);
+        isal_hip_enc_masks(b->k, b->rows, gftbls, &em);
+        e = hipMalloc((void **) &d_tbl, n * 4 + 4);
+        if (e == hipSuccess)
+                e = hipMemcpy(d_tbl, h, n * 4, hipMemcpyHostToDevice);
+        free(h);
+        if (e == hipSuccess && hx) {
+                /* the product tables are optional: without device memory for
+                 * them the batch's wide passes take the other kernels, and
+                 * the next launch must not find this failure as HIP's last
+                 * error */
+                if (BATCH_TRY_AT(FAULT_LDSX_ALLOC, hipMalloc((void **) &d_ldsx, nw * 8)) != hipSuccess) {
+                        (void) hipGetLastError();
+                        d_ldsx = NULL;
+                } else {
+                        e = BATCH_TRY_AT(FAULT_LDSX_H2D, hipMemcpy(d_ldsx, hx, nw * 8, hipMemcpyHostToDevice));
+                }
+        }
+        free(hx);
+        /* launches already queued on any (possibly non-blocking) stream may
+         * still read the old tables: let them finish before those are freed */
+        if (e == hipSuccess && b->d_tbl)
+                e = hipDeviceSynchronize();
+        if (e != hipSuccess) {
+                (void) hipGetLastError();
+                if (d_tbl)
+                        (void) hipFree(d_tbl);
+                if (d_ldsx)
+                        (void) hipFree(d_ldsx);
                 return ISAL_HIP_EHIP;
+        }
+        if (b->d_tbl)
+                (void) hipFree(b->d_tbl);
+        if (b->d_ldsx)
+                (void) hipFree(b->d_ldsx);
+        b->d_tbl = d_tbl;
+        b->d_ldsx = d_ldsx;
         b->xr = xr;
         b->em = em;
         b->em.ldsx = b->d_ldsx;

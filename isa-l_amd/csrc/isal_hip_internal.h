@@ -288,6 +288,23 @@ long long isal_hip_knob(int id);
 /* bumped by every isal_hip_config_reload(): caches derived from knobs check it */
 unsigned isal_hip_knob_generation(void);
 
+/* Fault injection (tests): ISAL_HIP_FAULT=<site> makes the HIP call at that
+ * site fail as if it had returned an error, without issuing it — the code
+ * after the failure then runs for real. Sites 1-5 are those of every
+ * GPU-routed drop-in call (isal_hip_shim.c, where the fallback paths run);
+ * 6-7 those of isal_hip_batch_set_tables (isal_hip_batch.c). Sites: */
+enum {
+        FAULT_NONE = 0,
+        FAULT_ALLOC = 1,  /* staging / argument buffer allocation */
+        FAULT_H2D = 2,    /* a host-to-device copy */
+        FAULT_LAUNCH = 3, /* the kernel launch */
+        FAULT_D2H = 4,    /* the device-to-host copy of output row 1 (chunked) or of the outputs */
+        FAULT_SYNC = 5,   /* the final stream synchronisation */
+        FAULT_LDSX_ALLOC = 6, /* a batch's LDS product tables: their device allocation (tolerated:
+                           * the batch runs without them) */
+        FAULT_LDSX_H2D = 7,   /* ... their upload (the replacement fails, the batch keeps its tables) */
+};
+
 /* ---- the host (CPU) route (ec_cpu.c) ---------------------------------------
  * Same ops and return value as isal_hip_run, over HOST-resident shards only,
  * for columns [c0, len): the drop-in calls' route for small host calls, for

@@ -805,17 +805,10 @@ typedef struct {
 
 /* Fault injection (tests): ISAL_HIP_FAULT=<site> makes every GPU-routed call
  * fail at that site as if the HIP call there had returned an error, without
- * issuing it — the fallback paths then run for real. Sites: */
-enum {
-        FAULT_NONE = 0,
-        FAULT_ALLOC = 1,  /* staging / argument buffer allocation */
-        FAULT_H2D = 2,    /* a host-to-device copy */
-        FAULT_LAUNCH = 3, /* the kernel launch */
-        FAULT_D2H = 4,    /* the device-to-host copy of output row 1 (chunked) or of the outputs */
-        FAULT_SYNC = 5,   /* the final stream synchronisation */
-};
-
-/* ISAL_HIP_FAULT_CHUNK=n narrows the fault to column chunk n of a call, so
+ * issuing it — the fallback paths then run for real. The sites (FAULT_*) are
+ * listed in isal_hip_internal.h.
+ *
+ * ISAL_HIP_FAULT_CHUNK=n narrows the fault to column chunk n of a call, so
  * the fallback also runs after earlier chunks finished on the GPU. */
 static int
 fault_at(int site, long long chunk)
