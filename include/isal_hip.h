@@ -184,6 +184,58 @@ int isal_hip_repair_run(isal_hip_repair *r, void *stream);
 int isal_hip_repair_npatterns(const isal_hip_repair *r);
 int isal_hip_repair_destroy(isal_hip_repair *r);
 
+/* ---- overwrite batch: partial-stripe writes folded into parity ----------- */
+
+/*
+ * A read-modify-write of stripes that are already encoded: a client rewrites
+ * nw of a stripe's k data shards and the parity must become
+ *   coding[l] ^= C[l][j] * (old_j ^ new_j)   for every rewritten shard j, row l.
+ * An overwrite batch covers nstripes stripes of one geometry, each with its
+ * OWN set of nw rewritten shard indices, with one kernel launch per pass of
+ * isal_hip_max_rows_per_pass() rows, on the caller's stream; each parity row
+ * is read once and written once whatever nw is.
+ *   gftbls:   32*k*rows bytes from ec_init_tables for the encode matrix (host
+ *             memory; copied), as for isal_hip_batch_create.
+ *   idx:      nstripes*nw data-shard indices, idx[s*nw + i] in [0, k) for slot
+ *             i of stripe s (distinct within the stripe, any order);
+ *             1 <= nw <= k <= 256.
+ *   old_data: host array of nstripes*nw DEVICE pointers, old_data[s*nw + i] =
+ *             the bytes the parity currently reflects for that shard.
+ *   new_data: host array of nstripes*nw DEVICE pointers to the replacements.
+ *   coding:   host array of nstripes*rows DEVICE pointers (coding[s*rows + l]).
+ * len is the number of bytes rewritten. A sub-shard byte range is expressed
+ * by the caller: offset all of a stripe's pointers by the same amount and
+ * pass the range's length as len.
+ * Every pointer must be non-NULL and 16-byte aligned, and within one stripe no
+ * two of its 2*nw + rows byte ranges may overlap (ISAL_HIP_EINVAL); memory
+ * kinds and device ownership as for isal_hip_batch_create. Any len >= 0 is
+ * valid. *bad_stripe (optional) names the first stripe with a bad index,
+ * pointer or overlap on ISAL_HIP_EINVAL (-1 otherwise). All of these checks
+ * run before the first HIP call, so they answer the same on a host without a
+ * GPU. create uploads the pointer, index and coefficient tables once;
+ * isal_hip_overwrite_run only enqueues kernels. The object belongs to the
+ * caller's current device at creation and runs there.
+ *   flags = 0: only the parity changes. The delta is its own inverse, so
+ *     running twice restores the parity exactly.
+ *   flags = ISAL_HIP_OVERWRITE_COMMIT: the same pass also stores new over old
+ *     (in the last pass when rows exceed one pass), so that afterwards the old
+ *     location holds the current bytes; a second committed run finds a zero
+ *     delta and changes no byte.
+ *   Any other flag bit: ISAL_HIP_EINVAL, nothing enqueued.
+ * Out of scope: write counts that differ within one object (one object per
+ * count), unaligned or host-pageable shards, any CPU route, and overwrites of
+ * parity shards.
+ */
+#define ISAL_HIP_OVERWRITE_COMMIT 1
+typedef struct isal_hip_overwrite isal_hip_overwrite;
+int isal_hip_overwrite_create(isal_hip_overwrite **out, int len, int k, int rows,
+                              const unsigned char *gftbls, int nw, int nstripes,
+                              const unsigned char *idx, unsigned char *const *old_data,
+                              unsigned char *const *new_data, unsigned char *const *coding,
+                              int *bad_stripe);
+int isal_hip_overwrite_run(isal_hip_overwrite *o, int flags, void *stream);
+int isal_hip_overwrite_destroy(isal_hip_overwrite *o);
+
 /* ---- streaming pipeline for HOST-resident stripes ----------------------- */
 
 /*

@@ -1082,6 +1082,127 @@ hipError_t repair_pass(hipStream_t s, const uint64_t* ptrs, int ptr_stride, cons
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Overwrite: the partial-stripe write of an encoded stripe
+// (isal_hip_overwrite.c, DESIGN §3 "Overwrite batch"):
+//   coding[l] ^= c[l][j] * (old_j ^ new_j)   for the nw rewritten shards j
+// Row s of the pointer table holds nw old pointers, the nw new ones, then the
+// parity rows; idx[s * nw + i] is the data-shard index slot i rewrites. The
+// stripe comes from blockIdx, so the index is a scalar load that readfirstlane
+// pins to an SGPR, and column j's [P][kTbl] tables sit at tbl0 + j * P * kTbl
+// (tbl0 = the pass; the layout isal_hip_launch_update indexes with vec_i):
+// the coefficients stay scalar loads. The P parity vectors of the pass are
+// loaded once, held while the (old, new) pairs come in load groups of two
+// pairs, and stored once, whatever nw is. COMMIT also stores new over old
+// from the registers already loaded; the launcher sets it in a stripe's last
+// pass only (an earlier pass would leave the later rows a zero delta).
+// ---------------------------------------------------------------------------
+template <int P, bool COMMIT>
+__device__ __forceinline__ void overwrite_bytes(const uint64_t* __restrict__ sp, const uint32_t* __restrict__ ip,
+                                                int nw, int dst0, const uint32_t* __restrict__ tbl0, long long off,
+                                                int nb) {
+  for (int b = 0; b < nb; ++b) {
+    uint32_t acc[P];
+#pragma unroll
+    for (int l = 0; l < P; ++l) acc[l] = reinterpret_cast<const uint8_t*>(sp[dst0 + l])[off + b];
+    for (int i = 0; i < nw; ++i) {
+      uint8_t* o = reinterpret_cast<uint8_t*>(sp[i]) + off + b;
+      const uint8_t n = reinterpret_cast<const uint8_t*>(sp[nw + i])[off + b];
+      const Sel s = split(static_cast<uint32_t>(*o ^ n));
+      if constexpr (COMMIT) *o = n;
+      const unsigned j = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(ip[i])));
+      const uint32_t* __restrict__ t = tbl0 + static_cast<size_t>(j) * P * kTbl;
+#pragma unroll
+      for (int l = 0; l < P; ++l) acc[l] ^= gf_mul4(load_coef(t + l * kTbl), s);
+    }
+#pragma unroll
+    for (int l = 0; l < P; ++l) reinterpret_cast<uint8_t*>(sp[dst0 + l])[off + b] = static_cast<uint8_t>(acc[l]);
+  }
+}
+
+// Slots i..i+U-1 of one stripe: all 2U loads issued before any arithmetic.
+template <int P, int U, bool COMMIT>
+__device__ __forceinline__ void overwrite_group(uint32_t (&acc)[P][4], const uint64_t* __restrict__ sp,
+                                                const uint32_t* __restrict__ ip, int i, int nw,
+                                                const uint32_t* __restrict__ tbl0, long long off, int len) {
+  uint4 x[U], n[U];
+  const uint32_t* __restrict__ t[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    x[u] = load16<kBufNT>(sp[i + u], off, len);
+    n[u] = load16<kBufNT>(sp[nw + i + u], off, len);
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const unsigned j = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(ip[i + u])));
+    t[u] = tbl0 + static_cast<size_t>(j) * P * kTbl;
+    if constexpr (COMMIT) store16<kBufNT>(sp[i + u], off, n[u], len);
+    x[u].x ^= n[u].x;
+    x[u].y ^= n[u].y;
+    x[u].z ^= n[u].z;
+    x[u].w ^= n[u].w;
+  }
+  if constexpr (U == 2 && enc_pair<P, kEncLUT>() == 2) {
+    mac16x2<P>(acc, x[0], x[1], t[0], t[1]);
+  } else {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      mac16<P>(acc, x[u], t[u]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+}
+
+template <int P, bool COMMIT, int B>
+__global__ __launch_bounds__(B) void ec_overwrite_v16(const uint64_t* __restrict__ ptrs, int ptr_stride,
+                                                      const uint32_t* __restrict__ idx,
+                                                      const uint32_t* __restrict__ tbl0, int nw, int dst0, int len,
+                                                      unsigned nitems, unsigned tiles) {
+  for (unsigned w = blockIdx.x; w < nitems; w += gridDim.x) {
+    const unsigned stripe = w / tiles;
+    const unsigned tile = w - stripe * tiles;
+    const uint64_t* __restrict__ sp = ptrs + static_cast<size_t>(stripe) * ptr_stride;
+    const uint32_t* __restrict__ ip = idx + static_cast<size_t>(stripe) * nw;
+    const long long off = static_cast<long long>(tile) * (B * kVec) + threadIdx.x * kVec;
+    if (off + kVec <= len) {
+      uint32_t acc[P][4];
+#pragma unroll
+      for (int l = 0; l < P; ++l) {
+        const uint4 d = load16<kBufNT>(sp[dst0 + l], off, len);
+        acc[l][0] = d.x;
+        acc[l][1] = d.y;
+        acc[l][2] = d.z;
+        acc[l][3] = d.w;
+      }
+      int i = 0;
+      for (; i + 2 <= nw; i += 2) overwrite_group<P, 2, COMMIT>(acc, sp, ip, i, nw, tbl0, off, len);
+      if (i < nw) overwrite_group<P, 1, COMMIT>(acc, sp, ip, i, nw, tbl0, off, len);
+#pragma unroll
+      for (int l = 0; l < P; ++l)
+        store16<kBufNT>(sp[dst0 + l], off, make_uint4(acc[l][0], acc[l][1], acc[l][2], acc[l][3]), len);
+    } else if (off < len) {
+      overwrite_bytes<P, COMMIT>(sp, ip, nw, dst0, tbl0, off, static_cast<int>(len - off));
+    }
+  }
+}
+
+// One pass of P rows over nstripes table rows: the update kernel's 128-lane
+// workgroups and 2 KiB column tiles (kUpdBlock).
+template <int P>
+hipError_t overwrite_pass(hipStream_t s, const uint64_t* ptrs, int ptr_stride, const uint32_t* idx,
+                          const uint32_t* tbl0, int nw, int dst0, int len, unsigned nstripes, bool commit) {
+  const unsigned tiles = static_cast<unsigned>((static_cast<long long>(len) + kUpdTile - 1) / kUpdTile);
+  const unsigned nitems = nstripes * tiles;
+  if (commit)
+    ISAL_LAUNCH((ec_overwrite_v16<P, true, kUpdBlock>), dim3(grid_for(nitems)), dim3(kUpdBlock), 0, s, ptrs,
+                ptr_stride, idx, tbl0, nw, dst0, len, nitems, tiles);
+  else
+    ISAL_LAUNCH((ec_overwrite_v16<P, false, kUpdBlock>), dim3(grid_for(nitems)), dim3(kUpdBlock), 0, s, ptrs,
+                ptr_stride, idx, tbl0, nw, dst0, len, nitems, tiles);
+  isal_hip_count_launch();
+  return hipGetLastError();
+}
+
 }  // namespace
 
 // The 0/1 masks of a call, or none under ISAL_HIP_ENC_XOR=0 (read at launch,
@@ -1144,6 +1265,36 @@ extern "C" int isal_hip_launch_repair(const uint64_t* d_ptrs, int ptr_stride, co
 #define EC_CASE(n)                                                                                   \
   case n:                                                                                            \
     e = repair_pass<n>(s, ptrs, ptr_stride, d_pat + s0, tbl0, tbl_stride, k + r0, len, k, ns);       \
+    break;
+        EC_CASE(1) EC_CASE(2) EC_CASE(3) EC_CASE(4) EC_CASE(5) EC_CASE(6) EC_CASE(7) EC_CASE(8)
+#undef EC_CASE
+      }
+      if (e != hipSuccess) return static_cast<int>(e);
+    }
+  }
+  return 0;
+}
+
+extern "C" int isal_hip_launch_overwrite(const uint64_t* d_ptrs, int ptr_stride, const uint32_t* d_idx,
+                                         const uint32_t* d_tbl, int len, int k, int rows, int nw,
+                                         long long nstripes, int commit, void* stream) {
+  if (len <= 0 || rows <= 0 || nw <= 0 || nstripes <= 0) return 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned per = stripes_per_launch(len, true, kUpdTile);
+  for (long long s0 = 0; s0 < nstripes; s0 += per) {
+    const unsigned ns = static_cast<unsigned>(nstripes - s0 < per ? nstripes - s0 : per);
+    const uint64_t* ptrs = d_ptrs + s0 * ptr_stride;
+    const uint32_t* idx = d_idx + s0 * nw;
+    for (int r0 = 0; r0 < rows; r0 += EC_MAX_ROWS_PER_PASS) {
+      const int P = rows - r0 < EC_MAX_ROWS_PER_PASS ? rows - r0 : EC_MAX_ROWS_PER_PASS;
+      const uint32_t* tbl0 = d_tbl + static_cast<size_t>(kTbl) * k * r0;
+      // new goes over old only once every row of the stripe has seen the delta
+      const bool last = commit && r0 + P == rows;
+      hipError_t e = hipSuccess;
+      switch (P) {
+#define EC_CASE(n)                                                                          \
+  case n:                                                                                   \
+    e = overwrite_pass<n>(s, ptrs, ptr_stride, idx, tbl0, nw, 2 * nw + r0, len, ns, last); \
     break;
         EC_CASE(1) EC_CASE(2) EC_CASE(3) EC_CASE(4) EC_CASE(5) EC_CASE(6) EC_CASE(7) EC_CASE(8)
 #undef EC_CASE

@@ -248,6 +248,16 @@ int isal_hip_launch_repair(const uint64_t *d_ptrs, int ptr_stride, const uint32_
                            const uint32_t *d_tbl, unsigned tbl_stride, int len, int k, int rows,
                            long long nrows, void *stream);
 
+/* Overwrite (ec_kernels.hip ec_overwrite_v16): for each of the nstripes rows
+ * of a pointer table (nw old shards, the nw new ones, then rows parity rows,
+ * stride ptr_stride = 2 * nw + rows, every pointer 16-byte aligned),
+ * coding[l] ^= c[l][j] * (old ^ new) with j = d_idx[row * nw + slot]; d_tbl is
+ * one encode's tables (passes of EC_MAX_ROWS_PER_PASS rows). commit: the last
+ * pass also stores new over old. */
+int isal_hip_launch_overwrite(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_idx,
+                              const uint32_t *d_tbl, int len, int k, int rows, int nw,
+                              long long nstripes, int commit, void *stream);
+
 /* Kernel registry (isal_hip_selftest_kernels): every kernel a launcher can
  * launch registers its host handle and a name when the library loads
  * (ec_device.h ISAL_LAUNCH). */

@@ -111,6 +111,10 @@ def lib() -> ctypes.CDLL:
             "isal_hip_repair_run": (i, [ctypes.c_void_p, ctypes.c_void_p]),
             "isal_hip_repair_npatterns": (i, [ctypes.c_void_p]),
             "isal_hip_repair_destroy": (i, [ctypes.c_void_p]),
+            "isal_hip_overwrite_create": (i, [ctypes.POINTER(ctypes.c_void_p), i, i, i, _u8p, i, i, _u8p, _u8pp, _u8pp,
+                                              _u8pp, ctypes.POINTER(ctypes.c_int)]),
+            "isal_hip_overwrite_run": (i, [ctypes.c_void_p, i, ctypes.c_void_p]),
+            "isal_hip_overwrite_destroy": (i, [ctypes.c_void_p]),
             "isal_hip_pipe_create": (i, [ctypes.POINTER(ctypes.c_void_p), i, i, i, _u8p, i, i]),
             "isal_hip_pipe_submit": (i, [ctypes.c_void_p, _u8pp, _u8pp]),
             "isal_hip_pipe_flush": (i, [ctypes.c_void_p]),
@@ -418,6 +422,50 @@ class Repair:
     def close(self) -> None:
         if getattr(self, "_h", None):
             lib().isal_hip_repair_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+OVERWRITE_COMMIT = 1  # ISAL_HIP_OVERWRITE_COMMIT
+
+
+class Overwrite:
+    """nstripes encoded stripes of one geometry, each with its own nw rewritten
+    data shards, whose deltas are folded into the parity by one launch per pass
+    (include/isal_hip.h overwrite batch).
+
+    idx[s*nw + i] is the data-shard index slot i of stripe s rewrites;
+    old_data / new_data[s*nw + i] and coding[s*rows + l] are addresses (or
+    tensors) of 16-byte aligned device buffers. run() only enqueues on
+    `stream`; commit=True also stores new over old in the same pass."""
+
+    def __init__(self, len_: int, k: int, rows: int, gftbls, nw: int, nstripes: int, idx: Sequence[int],
+                 old_data: Sequence, new_data: Sequence, coding: Sequence):
+        if (len(idx) != nstripes * nw or len(old_data) != nstripes * nw or len(new_data) != nstripes * nw
+                or len(coding) != nstripes * rows):
+            raise ValueError("idx, old_data and new_data must hold nstripes*nw entries and coding nstripes*rows")
+        ix = np.array(list(idx), dtype=np.uint8)
+        h, bad = ctypes.c_void_p(), ctypes.c_int(-1)
+        rc = lib().isal_hip_overwrite_create(ctypes.byref(h), len_, k, rows, _p(gftbls), nw, nstripes, _p(ix),
+                                             _pp(old_data), _pp(new_data), _pp(coding), ctypes.byref(bad))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_overwrite_create failed ({rc}, stripe {bad.value})")
+        self.len, self.k, self.rows, self.nw, self.nstripes = len_, k, rows, nw, nstripes
+        self._h = h
+
+    def run(self, commit: bool = False, stream: int = 0) -> None:
+        rc = lib().isal_hip_overwrite_run(self._h, OVERWRITE_COMMIT if commit else 0, ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_overwrite_run failed ({rc})")
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().isal_hip_overwrite_destroy(self._h)
             self._h = None
 
     def __del__(self):
