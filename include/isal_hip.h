@@ -236,6 +236,98 @@ int isal_hip_overwrite_create(isal_hip_overwrite **out, int len, int k, int rows
 int isal_hip_overwrite_run(isal_hip_overwrite *o, int flags, void *stream);
 int isal_hip_overwrite_destroy(isal_hip_overwrite *o);
 
+/* ---- scrub batch: the corrupt shard of each bad stripe in one pass -------- */
+
+/*
+ * isal_hip_batch_check says that a stripe is inconsistent; a scrub batch also
+ * says which shard to rebuild, from the parity the check recomputes anyway.
+ * Shard index i < k is data shard i, index k + l is parity row l. C[l][j] is
+ * the coefficient of row l and source j: byte 1 of the 32-byte entry
+ * gftbls + 32*(l*k + j) (the ec_init_tables format).
+ *
+ * Per byte column, let e[l] = stored parity row l ^ the parity row l
+ * recomputed from the stored sources (the column's syndrome). If every e[l]
+ * is zero the column is consistent. Otherwise the column NAMES
+ *   - data shard j < k, when some d != 0 gives e[l] == C[l][j]*d for every l;
+ *   - parity row l (index k + l), when e is non-zero in row l only;
+ *   - nothing, when neither holds.
+ * Per stripe, after isal_hip_scrub_run, verdict[s] is
+ *   - ISAL_HIP_SCRUB_CLEAN when no byte column mismatches;
+ *   - shard index i when every mismatching column names the same i;
+ *   - ISAL_HIP_SCRUB_MULTI when two columns name different shards or some
+ *     column names nothing;
+ * whichever lane or workgroup found what first.
+ *
+ * What a verdict is worth: an index is THE ONLY SINGLE-SHARD EXPLANATION of
+ * the stripe's mismatches, not a proof that this shard is the corrupt one.
+ * Two corrupt shards in one byte column can imitate a third: with rows = 2
+ * about (k + 2)/257 of random two-shard syndromes do. Only the agreement of
+ * all of a stripe's mismatching columns makes that rare (a single corrupt
+ * byte column carries no such agreement). Callers who keep fragment checksums
+ * (isal_hip_batch_crc) should confirm the verdict with them before they
+ * rebuild the named shard through isal_hip_repair_create(nerrs = 1).
+ */
+#define ISAL_HIP_SCRUB_CLEAN 0xffffffffu /* every byte column consistent */
+#define ISAL_HIP_SCRUB_MULTI 0xfffffffeu /* inconsistent, and no single shard explains it */
+
+/*
+ * Pure host arithmetic, no GPU; k >= 1, rows >= 1, k + rows <= 256.
+ * isal_hip_scrub_ambiguity: 0 when the k + rows columns of [C | I_rows] are
+ *   all non-zero and no two are proportional, so that at most one shard can
+ *   explain any syndrome. Otherwise ISAL_HIP_ESINGULAR, and pair (optional)
+ *   holds the first offending pair in lexicographic order; a zero column j is
+ *   reported as {j, j}. ISAL_HIP_EINVAL for arguments outside the contract
+ *   (pair is {-1, -1} whenever the answer is not ISAL_HIP_ESINGULAR).
+ * isal_hip_locate_syndrome: the per-column rule above for one syndrome of
+ *   rows bytes: the shard index it names (for a matrix that
+ *   isal_hip_scrub_ambiguity refuses: the lowest data shard that explains it,
+ *   before any parity row), (int) ISAL_HIP_SCRUB_MULTI when it names nothing,
+ *   (int) ISAL_HIP_SCRUB_CLEAN when it is all zero. Both constants are
+ *   negative as int, so no error code can be told from them: arguments
+ *   outside the contract answer (int) ISAL_HIP_SCRUB_MULTI, no shard.
+ */
+int isal_hip_scrub_ambiguity(int k, int rows, const unsigned char *gftbls, int pair[2]);
+int isal_hip_locate_syndrome(int k, int rows, const unsigned char *gftbls,
+                             const unsigned char *syndrome);
+
+/*
+ * A scrub batch covers nstripes stripes of one geometry; len, k, rows,
+ * gftbls, data and coding as for isal_hip_batch_create, *bad_stripe
+ * (optional) as for the repair and overwrite batches. Refused, all before the
+ * first HIP call, so a host without a GPU answers the same:
+ *   ISAL_HIP_EINVAL    NULL arguments, len < 0, nstripes <= 0, k < 1,
+ *                      k + rows > 256, or rows < 2 (one row cannot tell
+ *                      shards apart);
+ *   ISAL_HIP_EINVAL    rows > isal_hip_max_rows_per_pass(): a syndrome must be
+ *                      whole inside one workgroup; wider codes are out of
+ *                      scope;
+ *   ISAL_HIP_EINVAL    a NULL shard pointer or one not 16-byte aligned;
+ *                      *bad_stripe names the first such stripe (-1 otherwise);
+ *   ISAL_HIP_ESINGULAR a matrix that isal_hip_scrub_ambiguity refuses.
+ * Memory kinds and device ownership as for isal_hip_batch_create. The object
+ * belongs to the caller's current device at creation and runs there. Pointer,
+ * coefficient and location tables are uploaded once in create;
+ * isal_hip_scrub_run only enqueues on the caller's stream: a fill of verdict
+ * (a DEVICE array of nstripes words) with ISAL_HIP_SCRUB_CLEAN, then one
+ * kernel launch (one per slice of stripes for very large batches, counted by
+ * isal_hip_kernel_launches). Every word of verdict is rewritten by each call
+ * with len > 0; with len == 0 the call returns 0 and enqueues nothing.
+ * Nothing is written to the shards. Consistent data costs what
+ * isal_hip_batch_check costs: the location arithmetic runs only in lanes that
+ * hold a mismatching byte.
+ * Out of scope: more than isal_hip_max_rows_per_pass() rows, locating two or
+ * more corrupt shards, correcting in the same pass (rebuild through the
+ * repair batch), unaligned or host-pageable shards, and any CPU route beyond
+ * the two host functions above.
+ */
+typedef struct isal_hip_scrub isal_hip_scrub;
+int isal_hip_scrub_create(isal_hip_scrub **out, int len, int k, int rows,
+                          const unsigned char *gftbls, int nstripes,
+                          unsigned char *const *data, unsigned char *const *coding,
+                          int *bad_stripe);
+int isal_hip_scrub_run(isal_hip_scrub *s, unsigned int *verdict, void *stream);
+int isal_hip_scrub_destroy(isal_hip_scrub *s);
+
 /* ---- streaming pipeline for HOST-resident stripes ----------------------- */
 
 /*

@@ -467,6 +467,145 @@ __global__ __launch_bounds__(kBlock) void ec_verify_b1(const uint64_t* __restric
 }
 
 // ---------------------------------------------------------------------------
+// Locate (the scrub batch, isal_hip_scrub.c, DESIGN §3 "Scrub batch"): the
+// batch verify whose mismatch branch names the shard that explains the
+// syndrome e[l] = stored row l ^ recomputed row l of a byte column, and folds
+// the answer into verdict[stripe]. One pass only (rows <= 8): a syndrome is
+// whole inside one lane. Nothing is written to the shards.
+// loc: the matrix as the cold path reads it, bytes: [rows][k] coefficients,
+// then per column its first row with a non-zero coefficient (0xff: none) and
+// that coefficient's inverse.
+// ---------------------------------------------------------------------------
+constexpr unsigned kScrubClean = 0xffffffffu, kScrubMulti = 0xfffffffeu;
+
+// Plain shift-and-reduce product in GF(2^8) mod 0x11d: no tables, corrupt
+// bytes only.
+__device__ __forceinline__ uint32_t gf_mul_slow(uint32_t a, uint32_t b) {
+  uint32_t r = 0;
+  for (int i = 0; i < 8; ++i) {
+    if (b & 1u) r ^= a;
+    b >>= 1;
+    a <<= 1;
+    if (a & 0x100u) a ^= 0x11du;
+  }
+  return r;
+}
+
+// One byte column's non-zero syndrome (row l in byte l of e): data shard j
+// when e = C[:, j] * d for some d != 0, parity row l (as k + l) when only row
+// l is non-zero, else nothing (kScrubMulti); folded into *w. The fold is
+// order-free: the first answer replaces kScrubClean, a different one (or
+// "nothing") turns the word into kScrubMulti, which absorbs.
+__device__ __noinline__ void locate_fold(const uint8_t* __restrict__ loc, int k, int rows, unsigned long long e,
+                                         unsigned* w) {
+  unsigned v = kScrubMulti;
+  const uint8_t* piv = loc + rows * k;
+  const uint8_t* inv = piv + k;
+  for (int j = 0; j < k && v == kScrubMulti; ++j) {
+    const unsigned p = piv[j];
+    if (p >= static_cast<unsigned>(rows)) continue;
+    const uint32_t d = gf_mul_slow(static_cast<uint32_t>(e >> (8 * p)) & 0xffu, inv[j]);
+    if (!d) continue;
+    int l = 0;
+    while (l < rows && gf_mul_slow(loc[l * k + j], d) == (static_cast<uint32_t>(e >> (8 * l)) & 0xffu)) ++l;
+    if (l == rows) v = static_cast<unsigned>(j);
+  }
+  if (v == kScrubMulti) {
+    for (int l = 0; l < rows; ++l)
+      if (e == ((e >> (8 * l)) & 0xffull) << (8 * l)) v = static_cast<unsigned>(k + l);
+  }
+  if (v != kScrubMulti) {
+    const unsigned old = atomicCAS(w, kScrubClean, v);
+    if (old == kScrubClean || old == v) return;
+  }
+  atomicExch(w, kScrubMulti);
+}
+
+// A lane's 16 syndrome bytes of P rows (x[l] = stored ^ recomputed), at least
+// one of them non-zero: every non-zero byte column goes to locate_fold.
+template <int P>
+__device__ __forceinline__ void locate_vec(const uint32_t (&x)[P][4], const uint8_t* __restrict__ loc, int k,
+                                           unsigned* w) {
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    uint32_t any = 0;
+#pragma unroll
+    for (int l = 0; l < P; ++l) any |= x[l][d];
+    if (!any) continue;
+#pragma unroll 1
+    for (int b = 0; b < 32; b += 8) {
+      if (!((any >> b) & 0xffu)) continue;
+      unsigned long long e = 0;
+#pragma unroll
+      for (int l = 0; l < P; ++l) e |= static_cast<unsigned long long>((x[l][d] >> b) & 0xffu) << (8 * l);
+      locate_fold(loc, k, P, e, w);
+    }
+  }
+}
+
+// Per-byte form (a ragged tile's last partial vector, len < 16): dot_bytes'
+// verify with the syndrome gathered per byte.
+template <int P>
+__device__ __forceinline__ void locate_bytes(const uint64_t* __restrict__ sp, const uint32_t* __restrict__ tbl, int k,
+                                             long long off, int nb, const uint8_t* __restrict__ loc, unsigned* w) {
+  for (int b = 0; b < nb; ++b) {
+    uint32_t acc[P];
+#pragma unroll
+    for (int l = 0; l < P; ++l) acc[l] = 0;
+    for (int j = 0; j < k; ++j) {
+      const Sel s = split(reinterpret_cast<const uint8_t*>(sp[j])[off + b]);
+#pragma unroll
+      for (int l = 0; l < P; ++l) acc[l] ^= gf_mul4(load_coef(tbl + (j * P + l) * kTbl), s);
+    }
+    unsigned long long e = 0;
+#pragma unroll
+    for (int l = 0; l < P; ++l)
+      e |= static_cast<unsigned long long>((acc[l] ^ reinterpret_cast<const uint8_t*>(sp[k + l])[off + b]) & 0xffu)
+           << (8 * l);
+    if (e) locate_fold(loc, k, P, e, w);
+  }
+}
+
+// verify_items' batch form (sources at [0, k), stored rows at [k, k + P) of a
+// stripe's pointers) with the mismatch branch replaced.
+template <int P, class Pol, int FL>
+__global__ __launch_bounds__(kBlock, (enc_waves<P, Pol::U, FL | kEncVerify>())) void ec_locate_v16(
+    const uint64_t* __restrict__ ptrs, int ptr_stride, const uint32_t* __restrict__ tbl, int len, int k,
+    unsigned nitems, unsigned tiles, unsigned long long r0m, unsigned c0m, const uint8_t* __restrict__ loc,
+    unsigned* __restrict__ verdict) {
+  for (unsigned ww = blockIdx.x; ww < nitems; ww += gridDim.x) {
+    const unsigned w = xcd_item(ww, nitems, 1);
+    const unsigned stripe = w / tiles;
+    const unsigned tile = w - stripe * tiles;
+    const uint64_t* __restrict__ sp = ptrs + static_cast<size_t>(stripe) * ptr_stride;
+    const long long off = static_cast<long long>(tile) * kTile + threadIdx.x * kVec;
+    if (off + kVec <= len) {
+      constexpr bool kEarly = P <= 3;  // as verify_items: the stored rows' latency under the fold
+      uint4 st[kEarly ? P : 1];
+      if constexpr (kEarly) {
+#pragma unroll
+        for (int l = 0; l < P; ++l) st[l] = load16<kBufNT>(sp[k + l], off, len);
+      }
+      uint32_t acc[P][4];
+      accum16<P, Pol, FL>(acc, sp, tbl, k, off, len, r0m, c0m);
+      uint32_t any = 0;
+#pragma unroll
+      for (int l = 0; l < P; ++l) {
+        const uint4 e = kEarly ? st[kEarly ? l : 0] : load16<kBufNT>(sp[k + l], off, len);
+        acc[l][0] ^= e.x;
+        acc[l][1] ^= e.y;
+        acc[l][2] ^= e.z;
+        acc[l][3] ^= e.w;
+        any |= (acc[l][0] | acc[l][1]) | (acc[l][2] | acc[l][3]);
+      }
+      if (__builtin_expect(any != 0, 0)) locate_vec<P>(acc, loc, k, verdict + stripe);
+    } else if (off < len) {
+      locate_bytes<P>(sp, tbl, k, off, static_cast<int>(len - off), loc, verdict + stripe);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Update: coding[l] ^= c[l][vec_i] * data  (ec_base.c:327-342, gf_vect_mad)
 // tbl points at the [P][5] tables of source vec_i for this pass.
 // ---------------------------------------------------------------------------
@@ -1533,6 +1672,50 @@ extern "C" int isal_hip_launch_verify_batch(const uint64_t* d_ptrs, int ptr_stri
       e = hipGetLastError();
       if (e != hipSuccess) return static_cast<int>(e);
     }
+  }
+  return 0;
+}
+
+// The scrub batch's launch: verdict (nstripes words) is filled with "clean" on
+// the stream, then one ec_locate_v16 launch per slice of stripes, with the
+// verify's load group and 0/1 form.
+extern "C" int isal_hip_launch_locate_batch(const uint64_t* d_ptrs, int ptr_stride, const uint32_t* d_tbl, int len,
+                                            int k, int rows, long long nstripes, const isal_hip_encmask* em,
+                                            const unsigned char* d_loc, unsigned* verdict, void* stream) {
+  if (len <= 0 || nstripes <= 0) return 0;
+  if (rows < 2 || rows > EC_MAX_ROWS_PER_PASS || k < 1) return static_cast<int>(hipErrorInvalidValue);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipError_t e = hipMemsetAsync(verdict, 0xff, static_cast<size_t>(nstripes) * 4, s);
+  if (e != hipSuccess) return static_cast<int>(e);
+  em = enc_xor_masks(em);
+  const bool x = em && (em->ok & 1u);
+  const unsigned long long r0m = x ? em->r0[0] : 0ull;
+  const unsigned c0m = x ? em->c0[0] : 0u;
+  const unsigned per = stripes_per_launch(len, true);
+  const unsigned tiles = static_cast<unsigned>((static_cast<long long>(len) + kTile - 1) / kTile);
+  const int U = verify_group(k);
+  for (long long s0 = 0; s0 < nstripes; s0 += per) {
+    const unsigned ns = static_cast<unsigned>(nstripes - s0 < per ? nstripes - s0 : per);
+    const uint64_t* ptrs = d_ptrs + s0 * ptr_stride;
+    const unsigned nitems = ns * tiles;
+    switch (rows * 64 + U * 2 + (x ? 1 : 0)) {
+#define EC_LCASE(n, u)                                                                                          \
+  case n * 64 + u * 2:                                                                                          \
+    ISAL_LAUNCH((ec_locate_v16<n, EncPol<u, kBufNT, kBufNT, 0>, kEncLUT>), dim3(nitems), dim3(kBlock), 0, s,    \
+                ptrs, ptr_stride, d_tbl, len, k, nitems, tiles, 0ull, 0u, d_loc, verdict + s0);                 \
+    break;                                                                                                      \
+  case n * 64 + u * 2 + 1:                                                                                      \
+    ISAL_LAUNCH((ec_locate_v16<n, EncPol<u, kBufNT, kBufNT, 0>, kEncXor>), dim3(nitems), dim3(kBlock), 0, s,    \
+                ptrs, ptr_stride, d_tbl, len, k, nitems, tiles, r0m, c0m, d_loc, verdict + s0);                 \
+    break;
+#define EC_LCASE_U(n) EC_LCASE(n, 10) EC_LCASE(n, 8) EC_LCASE(n, 6) EC_LCASE(n, 4)
+      EC_LCASE_U(2) EC_LCASE_U(3) EC_LCASE_U(4) EC_LCASE_U(5) EC_LCASE_U(6) EC_LCASE_U(7) EC_LCASE_U(8)
+#undef EC_LCASE_U
+#undef EC_LCASE
+    }
+    isal_hip_count_launch();
+    e = hipGetLastError();
+    if (e != hipSuccess) return static_cast<int>(e);
   }
   return 0;
 }

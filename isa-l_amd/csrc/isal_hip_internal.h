@@ -258,6 +258,18 @@ int isal_hip_launch_overwrite(const uint64_t *d_ptrs, int ptr_stride, const uint
                               const uint32_t *d_tbl, int len, int k, int rows, int nw,
                               long long nstripes, int commit, void *stream);
 
+/* Scrub (ec_kernels.hip ec_locate_v16): the batch verify (k sources then rows
+ * stored rows per pointer row, every pointer 16-byte aligned, one pass:
+ * 2 <= rows <= EC_MAX_ROWS_PER_PASS) whose mismatching byte columns name the
+ * shard that explains their syndrome; verdict (device, nstripes words) is set
+ * to "clean" on the stream before the kernels. d_loc, the matrix as the
+ * mismatch branch reads it (device bytes): [rows][k] coefficients, then per
+ * column its first row with a non-zero coefficient and that coefficient's
+ * inverse. */
+int isal_hip_launch_locate_batch(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_tbl, int len,
+                                 int k, int rows, long long nstripes, const isal_hip_encmask *em,
+                                 const unsigned char *d_loc, unsigned *verdict, void *stream);
+
 /* Kernel registry (isal_hip_selftest_kernels): every kernel a launcher can
  * launch registers its host handle and a name when the library loads
  * (ec_device.h ISAL_LAUNCH). */

@@ -26,7 +26,8 @@ __all__ = [
     "gf_invert_matrix", "gf_vect_mul_init", "ec_init_tables", "ec_encode_data",
     "ec_encode_data_base", "ec_encode_data_update", "ec_encode_data_update_base",
     "gf_vect_dot_prod", "gf_vect_dot_prod_base", "gf_vect_mad", "gf_vect_mad_base",
-    "gf_vect_mul", "gf_vect_mul_base", "Batch", "Repair", "decode_matrix", "ESINGULAR", "Pipe", "kernel_launches", "max_rows_per_pass",
+    "gf_vect_mul", "gf_vect_mul_base", "Batch", "Repair", "decode_matrix", "ESINGULAR", "Scrub", "scrub_ambiguity",
+    "locate_syndrome", "SCRUB_CLEAN", "SCRUB_MULTI", "Pipe", "kernel_launches", "max_rows_per_pass",
     "version", "addr", "cpu_calls", "fallbacks", "reload_config", "Multi", "partition",
     "route_device", "contexts_created", "selftest_kernels", "crc32_iscsi", "crc64", "CRC64_VARIANTS", "slow_waits",
 ]
@@ -115,6 +116,12 @@ def lib() -> ctypes.CDLL:
                                               _u8pp, ctypes.POINTER(ctypes.c_int)]),
             "isal_hip_overwrite_run": (i, [ctypes.c_void_p, i, ctypes.c_void_p]),
             "isal_hip_overwrite_destroy": (i, [ctypes.c_void_p]),
+            "isal_hip_scrub_ambiguity": (i, [i, i, _u8p, ctypes.POINTER(ctypes.c_int)]),
+            "isal_hip_locate_syndrome": (i, [i, i, _u8p, _u8p]),
+            "isal_hip_scrub_create": (i, [ctypes.POINTER(ctypes.c_void_p), i, i, i, _u8p, i, _u8pp, _u8pp,
+                                          ctypes.POINTER(ctypes.c_int)]),
+            "isal_hip_scrub_run": (i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+            "isal_hip_scrub_destroy": (i, [ctypes.c_void_p]),
             "isal_hip_pipe_create": (i, [ctypes.POINTER(ctypes.c_void_p), i, i, i, _u8p, i, i]),
             "isal_hip_pipe_submit": (i, [ctypes.c_void_p, _u8pp, _u8pp]),
             "isal_hip_pipe_flush": (i, [ctypes.c_void_p]),
@@ -466,6 +473,76 @@ class Overwrite:
     def close(self) -> None:
         if getattr(self, "_h", None):
             lib().isal_hip_overwrite_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+SCRUB_CLEAN = 0xFFFFFFFF  # ISAL_HIP_SCRUB_CLEAN
+SCRUB_MULTI = 0xFFFFFFFE  # ISAL_HIP_SCRUB_MULTI
+
+
+def scrub_ambiguity(k: int, rows: int, gftbls):
+    """isal_hip_scrub_ambiguity (host arithmetic, no GPU): None when no two of
+    the k + rows columns of [C | I] are proportional and none is zero, else
+    the first offending pair (a, b) of shard indices ((j, j): a zero column)."""
+    g = _u8(gftbls)
+    if k < 1 or rows < 1 or g.size < 32 * k * rows:
+        raise ValueError("gftbls must hold 32*k*rows bytes")
+    pair = (ctypes.c_int * 2)(-1, -1)
+    rc = lib().isal_hip_scrub_ambiguity(k, rows, _p(g), pair)
+    if rc == 0:
+        return None
+    if rc != ESINGULAR:
+        raise ValueError(f"isal_hip_scrub_ambiguity failed ({rc})")
+    return int(pair[0]), int(pair[1])
+
+
+def locate_syndrome(k: int, rows: int, gftbls, syndrome) -> int:
+    """isal_hip_locate_syndrome (host arithmetic, no GPU): the shard index the
+    rows-byte syndrome (stored ^ recomputed parity of one byte column) names,
+    SCRUB_MULTI when it names nothing, SCRUB_CLEAN when it is all zero."""
+    g, e = _u8(gftbls), _u8(syndrome)
+    if k < 1 or rows < 1 or k + rows > 256 or g.size < 32 * k * rows or e.size != rows:
+        raise ValueError("gftbls must hold 32*k*rows bytes and syndrome rows bytes, k + rows <= 256")
+    return int(lib().isal_hip_locate_syndrome(k, rows, _p(g), _p(e))) & 0xFFFFFFFF
+
+
+class Scrub:
+    """nstripes encoded stripes of one geometry, verified by one launch that
+    names, for every inconsistent stripe, the one shard that explains its
+    mismatches (include/isal_hip.h scrub batch).
+
+    data[s*k + j] / coding[s*rows + l] are addresses (or tensors) of 16-byte
+    aligned device buffers, as for Batch. run() only enqueues on `stream`:
+    the DEVICE buffer verdict (nstripes uint32) gets SCRUB_CLEAN, a shard index
+    (j < k: data shard j, k + l: parity row l) or SCRUB_MULTI per stripe. An
+    index is the only single-shard explanation, not a proof: confirm it with
+    fragment checksums where they exist, then rebuild with Repair(nerrs=1)."""
+
+    def __init__(self, len_: int, k: int, rows: int, gftbls, nstripes: int, data: Sequence, coding: Sequence):
+        if len(data) != nstripes * k or len(coding) != nstripes * rows:
+            raise ValueError("pointer lists must hold nstripes*k and nstripes*rows entries")
+        h, bad = ctypes.c_void_p(), ctypes.c_int(-1)
+        rc = lib().isal_hip_scrub_create(ctypes.byref(h), len_, k, rows, _p(gftbls), nstripes, _pp(data),
+                                         _pp(coding), ctypes.byref(bad))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_scrub_create failed ({rc}, stripe {bad.value})")
+        self.len, self.k, self.rows, self.nstripes = len_, k, rows, nstripes
+        self._h = h
+
+    def run(self, verdict, stream: int = 0) -> None:
+        rc = lib().isal_hip_scrub_run(self._h, ctypes.c_void_p(addr(verdict)), ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_scrub_run failed ({rc})")
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().isal_hip_scrub_destroy(self._h)
             self._h = None
 
     def __del__(self):
