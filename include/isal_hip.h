@@ -328,6 +328,74 @@ int isal_hip_scrub_create(isal_hip_scrub **out, int len, int k, int rows,
 int isal_hip_scrub_run(isal_hip_scrub *s, unsigned int *verdict, void *stream);
 int isal_hip_scrub_destroy(isal_hip_scrub *s);
 
+/* ---- ragged batch: stripes of different lengths in one launch ------------- */
+
+/*
+ * Every object above takes one len for all of its stripes. An object store
+ * encodes objects of every size, and the last stripe of every object is
+ * short: a ragged batch covers nstripes stripes of one geometry (k sources,
+ * rows outputs, one matrix), each with its OWN shard length, and encodes or
+ * checks all of them with one kernel launch per pass of
+ * isal_hip_max_rows_per_pass() rows, on the caller's stream.
+ *   gftbls, data (nstripes*k DEVICE pointers), coding (nstripes*rows): as for
+ *           isal_hip_batch_create. gftbls is any ec_init_tables output, so a
+ *           uniform-pattern decode of ragged stripes is this object built
+ *           with the decode matrix (isal_hip_decode_matrix), data = the
+ *           survivors and coding = the shards to rebuild.
+ *   lens:   nstripes byte lengths; lens[s] is the length of every shard of
+ *           stripe s. Any value >= 0 is valid; a stripe of length 0 is
+ *           neither read nor written.
+ * Refused, all before the first HIP call, so a host without a GPU answers the
+ * same; *bad_stripe (optional) as for the repair, overwrite and scrub batches:
+ *   ISAL_HIP_EINVAL  NULL arguments, nstripes <= 0, k < 1, rows < 1 or
+ *                    k + rows > 256 (*bad_stripe = -1);
+ *   ISAL_HIP_EINVAL  a negative lens[s], a NULL shard pointer or one not
+ *                    16-byte aligned (those of zero-length stripes included);
+ *                    *bad_stripe names the first such stripe;
+ *   ISAL_HIP_EINVAL  more than 2^30 work items at the smallest tile (2 KiB),
+ *                    the limit of one launch: such a batch cannot exist in one
+ *                    GPU's memory, so it is refused, not sliced
+ *                    (*bad_stripe = -1).
+ * Memory kinds and device ownership as for isal_hip_batch_create. The object
+ * belongs to the caller's current device at creation and runs there.
+ * create uploads the pointer table, the coefficient tables, the lengths and
+ * the work-item tables once. Device memory besides the pointer and
+ * coefficient tables every batch has: 4 bytes per stripe, and 8 bytes per
+ * 4 KiB tile of one shard (0.2 % of one shard's bytes; a k-source stripe reads
+ * k times that); an object with rows % 8 == 1 or 2 runs a pass on 2 KiB tiles
+ * and keeps a second table of 8 bytes per 2 KiB tile.
+ *
+ * isal_hip_ragged_items: pure arithmetic, no GPU. The work items of a ragged
+ *   launch: the tiles of stripe 0, then of stripe 1, ...; stripe s has
+ *   ceil(lens[s] / tile) of them, a stripe of length 0 has none. Returns the
+ *   item count, or -1 for arguments outside the contract (NULL lens,
+ *   nstripes <= 0, a negative length, tile <= 0). items (optional): 2 words
+ *   per item, {stripe, tile index}.
+ * isal_hip_ragged_encode: only enqueues; one kernel launch per pass (counted
+ *   by isal_hip_kernel_launches). Stripe s's parity is byte-identical to
+ *   ec_encode_data(lens[s], ...). With every length 0 it returns 0 and
+ *   enqueues nothing.
+ * isal_hip_ragged_check: the isal_hip_batch_check contract per stripe. bad:
+ *   DEVICE array of nstripes words; bad[s] = ~0 when stripe s is consistent
+ *   or has length 0, else its first mismatch as column << 8 | row: the
+ *   smallest column, then the smallest row at that column, whichever lane,
+ *   workgroup or pass found it. Every word of bad is rewritten by each call,
+ *   unless every length is 0 (then nothing is enqueued). Nothing is written
+ *   to the shards.
+ * Out of scope: update, the fused checksums, the 0/1 XOR form and the
+ * LDS-staged and LDS product-table wide kernels of the uniform batch (every
+ * pass takes the plain lookup kernel), unaligned or host-pageable shards, any
+ * CPU route, and set_tables (one object per matrix).
+ */
+typedef struct isal_hip_ragged isal_hip_ragged;
+long long isal_hip_ragged_items(int nstripes, const int *lens, int tile, unsigned *items);
+int isal_hip_ragged_create(isal_hip_ragged **out, int k, int rows, const unsigned char *gftbls,
+                           int nstripes, const int *lens, unsigned char *const *data,
+                           unsigned char *const *coding, int *bad_stripe);
+int isal_hip_ragged_encode(isal_hip_ragged *r, void *stream);
+int isal_hip_ragged_check(isal_hip_ragged *r, unsigned long long *bad, void *stream);
+int isal_hip_ragged_destroy(isal_hip_ragged *r);
+
 /* ---- streaming pipeline for HOST-resident stripes ----------------------- */
 
 /*

@@ -1222,6 +1222,128 @@ hipError_t repair_pass(hipStream_t s, const uint64_t* ptrs, int ptr_stride, cons
 }
 
 // ---------------------------------------------------------------------------
+// Ragged batch (isal_hip_ragged.c, DESIGN §3 "Ragged batch"): every stripe has
+// its own shard length, so work item v is not (v / tiles, v % tiles) but row v
+// of an item table {stripe, tile} built on the host (isal_hip_ragged_items,
+// one table per tile size), and every load and store is bounded by
+// lens[stripe]. One workgroup per item; the item comes from blockIdx, so the
+// table row and the length are scalar loads that readfirstlane pins to SGPRs,
+// and the stripe's pointers and the coefficients stay scalar loads exactly as
+// in ec_encode_v16. The length load depends on the item load as the pointer
+// loads do, and is issued beside them. Always the plain lookup form (kEncLUT).
+// ---------------------------------------------------------------------------
+struct RagItem {
+  unsigned stripe, tile;
+  int len;
+};
+
+__device__ __forceinline__ RagItem rag_item(const uint2* __restrict__ items, const int* __restrict__ lens,
+                                            unsigned nitems) {
+  const uint2 it = items[xcd_item(blockIdx.x, nitems, 1)];
+  RagItem r;
+  r.stripe = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(it.x)));
+  r.tile = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(it.y)));
+  r.len = __builtin_amdgcn_readfirstlane(lens[r.stripe]);
+  return r;
+}
+
+// encode_items' body for one item: sources at [0, k), outputs at [dst0, dst0 + P)
+// of the stripe's pointers.
+template <int P, class Pol, int B>
+__global__ __launch_bounds__(B, (enc_waves<P, Pol::U, kEncLUT>())) void ec_encode_rag(
+    const uint64_t* __restrict__ ptrs, int ptr_stride, const uint2* __restrict__ items,
+    const int* __restrict__ lens, const uint32_t* __restrict__ tbl, int dst0, int k, unsigned nitems) {
+  if (blockIdx.x >= nitems) return;
+  const RagItem it = rag_item(items, lens, nitems);
+  const uint64_t* __restrict__ sp = ptrs + static_cast<size_t>(it.stripe) * ptr_stride;
+  const int len = it.len;
+  const long long off = static_cast<long long>(it.tile) * (B * kVec) + threadIdx.x * kVec;
+  if (off + kVec <= len) {
+    uint32_t acc[P][4];
+    accum16<P, Pol, kEncLUT>(acc, sp, tbl, k, off, len);
+#pragma unroll
+    for (int l = 0; l < P; ++l)
+      store16<Pol::ST>(sp[dst0 + l], off, make_uint4(acc[l][0], acc[l][1], acc[l][2], acc[l][3]), len);
+  } else if (off < len) {
+    dot_bytes<P>(sp, 0, dst0, tbl, k, off, static_cast<int>(len - off));
+  }
+}
+
+// verify_items' batch form for one item (4 KiB tiles): mismatches of rows
+// row0 .. row0 + P - 1 lower sbad[stripe]. Nothing is written to the shards.
+template <int P, class Pol>
+__global__ __launch_bounds__(kBlock, (enc_waves<P, Pol::U, kEncLUT | kEncVerify>())) void ec_verify_rag(
+    const uint64_t* __restrict__ ptrs, int ptr_stride, const uint2* __restrict__ items,
+    const int* __restrict__ lens, const uint32_t* __restrict__ tbl, int dst0, int row0, int k, unsigned nitems,
+    unsigned long long* __restrict__ sbad) {
+  if (blockIdx.x >= nitems) return;
+  const RagItem it = rag_item(items, lens, nitems);
+  const uint64_t* __restrict__ sp = ptrs + static_cast<size_t>(it.stripe) * ptr_stride;
+  unsigned long long* bad = sbad + it.stripe;
+  const int len = it.len;
+  const long long off = static_cast<long long>(it.tile) * kTile + threadIdx.x * kVec;
+  if (off + kVec <= len) {
+    constexpr bool kEarly = P <= 3;  // as verify_items: the stored rows' latency under the fold
+    uint4 st[kEarly ? P : 1];
+    if constexpr (kEarly) {
+#pragma unroll
+      for (int l = 0; l < P; ++l) st[l] = load16<kBufNT>(sp[dst0 + l], off, len);
+    }
+    uint32_t acc[P][4];
+    accum16<P, Pol, kEncLUT>(acc, sp, tbl, k, off, len);
+#pragma unroll
+    for (int l = 0; l < P; ++l) {
+      const uint4 e = kEarly ? st[kEarly ? l : 0] : load16<kBufNT>(sp[dst0 + l], off, len);
+      const uint32_t x[4] = {acc[l][0] ^ e.x, acc[l][1] ^ e.y, acc[l][2] ^ e.z, acc[l][3] ^ e.w};
+#pragma unroll
+      for (int d = 0; d < 4; ++d)
+        if (x[d]) {
+          note_mismatch(bad, off + 4 * d + (__builtin_ctz(x[d]) >> 3), row0 + l);
+          break;
+        }
+    }
+  } else if (off < len) {
+    dot_bytes<P, true>(sp, 0, dst0, tbl, k, off, static_cast<int>(len - off), bad, row0, 0);
+  }
+}
+
+// The host builds one item table per tile size (isal_hip_internal.h).
+static_assert(enc_block<1>() * kVec == ISAL_HIP_RAGGED_TILE_SMALL &&
+                  enc_block<ISAL_HIP_RAGGED_SMALL_ROWS>() * kVec == ISAL_HIP_RAGGED_TILE_SMALL &&
+                  enc_block<ISAL_HIP_RAGGED_SMALL_ROWS + 1>() * kVec == ISAL_HIP_RAGGED_TILE &&
+                  enc_block<EC_MAX_ROWS_PER_PASS>() * kVec == ISAL_HIP_RAGGED_TILE && kTile == ISAL_HIP_RAGGED_TILE &&
+                  kMaxItems == ISAL_HIP_RAGGED_MAX_ITEMS,
+              "isal_hip_ragged.c builds its item tables for these tiles and this item limit");
+
+// One pass of P rows over nitems items: block shape, occupancy cap, work
+// order and load group are the vector encode's (enc_block, enc_lds_alloc,
+// order 2, enc_group).
+template <int P, int U>
+void launch_encode_rag(hipStream_t s, const uint64_t* ptrs, int ptr_stride, const uint2* items, const int* lens,
+                       const uint32_t* tbl, int dst0, int k, unsigned nitems) {
+  constexpr int B = enc_block<P>();
+  if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2) fprintf(stderr, "isal_hip: kernel ec_encode_rag<%d, %d, %d>\n", P, U, B);
+  ISAL_LAUNCH((ec_encode_rag<P, EncPol<U, kBufNT, kBufNT, 2>, B>), dim3(grid_for(nitems)), dim3(B),
+              enc_lds_alloc(0, P), s, ptrs, ptr_stride, items, lens, tbl, dst0, k, nitems);
+}
+
+template <int P>
+hipError_t encode_rag_pass(hipStream_t s, const uint64_t* ptrs, int ptr_stride, const uint2* items, const int* lens,
+                           const uint32_t* tbl, int dst0, int k, unsigned nitems) {
+  switch (enc_group(k, P)) {
+#define EC_GROUP(u)                                                                  \
+  case u:                                                                            \
+    launch_encode_rag<P, u>(s, ptrs, ptr_stride, items, lens, tbl, dst0, k, nitems); \
+    break;
+    EC_GROUP(12) EC_GROUP(10) EC_GROUP(8) EC_GROUP(6) EC_GROUP(5)
+#undef EC_GROUP
+    default: launch_encode_rag<P, 4>(s, ptrs, ptr_stride, items, lens, tbl, dst0, k, nitems); break;
+  }
+  isal_hip_count_launch();
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // Overwrite: the partial-stripe write of an encoded stripe
 // (isal_hip_overwrite.c, DESIGN §3 "Overwrite batch"):
 //   coding[l] ^= c[l][j] * (old_j ^ new_j)   for the nw rewritten shards j
@@ -1712,6 +1834,70 @@ extern "C" int isal_hip_launch_locate_batch(const uint64_t* d_ptrs, int ptr_stri
       EC_LCASE_U(2) EC_LCASE_U(3) EC_LCASE_U(4) EC_LCASE_U(5) EC_LCASE_U(6) EC_LCASE_U(7) EC_LCASE_U(8)
 #undef EC_LCASE_U
 #undef EC_LCASE
+    }
+    isal_hip_count_launch();
+    e = hipGetLastError();
+    if (e != hipSuccess) return static_cast<int>(e);
+  }
+  return 0;
+}
+
+// The ragged batch's encode: one ec_encode_rag launch per pass of rows, each
+// over the item table of its tile size (passes of 1-2 rows: the small tiles).
+extern "C" int isal_hip_launch_encode_ragged(const uint64_t* d_ptrs, int ptr_stride, const uint32_t* d_tbl,
+                                             const int* d_lens, const unsigned* d_items, unsigned nitems,
+                                             const unsigned* d_items_small, unsigned nitems_small, int k, int rows,
+                                             void* stream) {
+  if (rows <= 0 || nitems == 0) return 0;  // every length 0: no tile of either size
+  if (k < 1 || nitems > kMaxItems || nitems_small > kMaxItems) return static_cast<int>(hipErrorInvalidValue);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int r0 = 0; r0 < rows; r0 += EC_MAX_ROWS_PER_PASS) {
+    const int P = rows - r0 < EC_MAX_ROWS_PER_PASS ? rows - r0 : EC_MAX_ROWS_PER_PASS;
+    const bool small = P <= ISAL_HIP_RAGGED_SMALL_ROWS;
+    const uint2* items = reinterpret_cast<const uint2*>(small ? d_items_small : d_items);
+    const unsigned n = small ? nitems_small : nitems;
+    const uint32_t* tbl = d_tbl + static_cast<size_t>(kTbl) * k * r0;
+    if (!items || n == 0) return static_cast<int>(hipErrorInvalidValue);
+    hipError_t e = hipSuccess;
+    switch (P) {
+#define EC_CASE(p)                                                                        \
+  case p:                                                                                 \
+    e = encode_rag_pass<p>(s, d_ptrs, ptr_stride, items, d_lens, tbl, k + r0, k, n); \
+    break;
+      EC_CASE(1) EC_CASE(2) EC_CASE(3) EC_CASE(4) EC_CASE(5) EC_CASE(6) EC_CASE(7) EC_CASE(8)
+#undef EC_CASE
+    }
+    if (e != hipSuccess) return static_cast<int>(e);
+  }
+  return 0;
+}
+
+// The ragged batch's check: bad (nstripes words) is filled with ~0 on the
+// stream, then one ec_verify_rag launch per pass over the 4 KiB item table,
+// with the verify's load group.
+extern "C" int isal_hip_launch_verify_ragged(const uint64_t* d_ptrs, int ptr_stride, const uint32_t* d_tbl,
+                                             const int* d_lens, const unsigned* d_items, unsigned nitems, int k,
+                                             int rows, long long nstripes, unsigned long long* bad, void* stream) {
+  if (rows <= 0 || nstripes <= 0 || nitems == 0) return 0;
+  if (k < 1 || nitems > kMaxItems || !d_items) return static_cast<int>(hipErrorInvalidValue);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipError_t e = hipMemsetAsync(bad, 0xff, static_cast<size_t>(nstripes) * 8, s);
+  if (e != hipSuccess) return static_cast<int>(e);
+  const uint2* items = reinterpret_cast<const uint2*>(d_items);
+  const int U = verify_group(k);
+  for (int r0 = 0; r0 < rows; r0 += EC_MAX_ROWS_PER_PASS) {
+    const int P = rows - r0 < EC_MAX_ROWS_PER_PASS ? rows - r0 : EC_MAX_ROWS_PER_PASS;
+    const uint32_t* tbl = d_tbl + static_cast<size_t>(kTbl) * k * r0;
+    switch (P * 16 + U) {
+#define EC_RCASE(p, u)                                                                                          \
+  case p * 16 + u:                                                                                              \
+    ISAL_LAUNCH((ec_verify_rag<p, EncPol<u, kBufNT, kBufNT, 0>>), dim3(nitems), dim3(kBlock), 0, s, d_ptrs,     \
+                ptr_stride, items, d_lens, tbl, k + r0, r0, k, nitems, bad);                                    \
+    break;
+#define EC_RCASE_U(p) EC_RCASE(p, 10) EC_RCASE(p, 8) EC_RCASE(p, 6) EC_RCASE(p, 4)
+      EC_RCASE_U(1) EC_RCASE_U(2) EC_RCASE_U(3) EC_RCASE_U(4) EC_RCASE_U(5) EC_RCASE_U(6) EC_RCASE_U(7) EC_RCASE_U(8)
+#undef EC_RCASE_U
+#undef EC_RCASE
     }
     isal_hip_count_launch();
     e = hipGetLastError();

@@ -270,6 +270,28 @@ int isal_hip_launch_locate_batch(const uint64_t *d_ptrs, int ptr_stride, const u
                                  int k, int rows, long long nstripes, const isal_hip_encmask *em,
                                  const unsigned char *d_loc, unsigned *verdict, void *stream);
 
+/* Ragged (ec_kernels.hip ec_encode_rag / ec_verify_rag): the batch encode and
+ * verify where stripe s has its own shard length d_lens[s] (device, nstripes
+ * ints). Pointer rows are k sources then rows outputs (stride ptr_stride,
+ * every pointer 16-byte aligned); d_tbl is one encode's tables. The work
+ * items come from device tables of {stripe, tile} word pairs as
+ * isal_hip_ragged_items builds them, one per tile size: passes of at most
+ * ISAL_HIP_RAGGED_SMALL_ROWS rows encode ISAL_HIP_RAGGED_TILE_SMALL-byte tiles
+ * (d_items_small, which may be NULL when rows has no such pass), every other
+ * pass and the verify ISAL_HIP_RAGGED_TILE-byte tiles. One launch per pass;
+ * nothing is enqueued when nitems == 0. bad: as isal_hip_launch_verify_batch. */
+#define ISAL_HIP_RAGGED_TILE 4096
+#define ISAL_HIP_RAGGED_TILE_SMALL 2048
+#define ISAL_HIP_RAGGED_SMALL_ROWS 2
+#define ISAL_HIP_RAGGED_MAX_ITEMS (1u << 30) /* ec_kernels.hip kMaxItems */
+int isal_hip_launch_encode_ragged(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_tbl,
+                                  const int *d_lens, const unsigned *d_items, unsigned nitems,
+                                  const unsigned *d_items_small, unsigned nitems_small, int k, int rows,
+                                  void *stream);
+int isal_hip_launch_verify_ragged(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_tbl,
+                                  const int *d_lens, const unsigned *d_items, unsigned nitems, int k,
+                                  int rows, long long nstripes, unsigned long long *bad, void *stream);
+
 /* Kernel registry (isal_hip_selftest_kernels): every kernel a launcher can
  * launch registers its host handle and a name when the library loads
  * (ec_device.h ISAL_LAUNCH). */

@@ -27,7 +27,7 @@ __all__ = [
     "ec_encode_data_base", "ec_encode_data_update", "ec_encode_data_update_base",
     "gf_vect_dot_prod", "gf_vect_dot_prod_base", "gf_vect_mad", "gf_vect_mad_base",
     "gf_vect_mul", "gf_vect_mul_base", "Batch", "Repair", "decode_matrix", "ESINGULAR", "Scrub", "scrub_ambiguity",
-    "locate_syndrome", "SCRUB_CLEAN", "SCRUB_MULTI", "Pipe", "kernel_launches", "max_rows_per_pass",
+    "locate_syndrome", "SCRUB_CLEAN", "SCRUB_MULTI", "Ragged", "ragged_items", "Pipe", "kernel_launches", "max_rows_per_pass",
     "version", "addr", "cpu_calls", "fallbacks", "reload_config", "Multi", "partition",
     "route_device", "contexts_created", "selftest_kernels", "crc32_iscsi", "crc64", "CRC64_VARIANTS", "slow_waits",
 ]
@@ -122,6 +122,13 @@ def lib() -> ctypes.CDLL:
                                           ctypes.POINTER(ctypes.c_int)]),
             "isal_hip_scrub_run": (i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
             "isal_hip_scrub_destroy": (i, [ctypes.c_void_p]),
+            "isal_hip_ragged_items": (ctypes.c_longlong, [i, ctypes.POINTER(ctypes.c_int), i,
+                                                          ctypes.POINTER(ctypes.c_uint)]),
+            "isal_hip_ragged_create": (i, [ctypes.POINTER(ctypes.c_void_p), i, i, _u8p, i, ctypes.POINTER(ctypes.c_int),
+                                           _u8pp, _u8pp, ctypes.POINTER(ctypes.c_int)]),
+            "isal_hip_ragged_encode": (i, [ctypes.c_void_p, ctypes.c_void_p]),
+            "isal_hip_ragged_check": (i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+            "isal_hip_ragged_destroy": (i, [ctypes.c_void_p]),
             "isal_hip_pipe_create": (i, [ctypes.POINTER(ctypes.c_void_p), i, i, i, _u8p, i, i]),
             "isal_hip_pipe_submit": (i, [ctypes.c_void_p, _u8pp, _u8pp]),
             "isal_hip_pipe_flush": (i, [ctypes.c_void_p]),
@@ -543,6 +550,67 @@ class Scrub:
     def close(self) -> None:
         if getattr(self, "_h", None):
             lib().isal_hip_scrub_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ragged_items(lens: Sequence[int], tile: int) -> np.ndarray:
+    """isal_hip_ragged_items (host arithmetic, no GPU): the work items of a
+    ragged launch over shards of lens[s] bytes in tiles of `tile` bytes, an
+    (n, 2) uint32 array of {stripe, tile index} rows."""
+    ln = np.array(list(lens), dtype=np.int32)
+    lp = ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+    n = int(lib().isal_hip_ragged_items(int(ln.size), lp, tile, None))
+    if n < 0:
+        raise ValueError("lens must be non-empty and non-negative, tile positive")
+    items = np.zeros((n, 2), dtype=np.uint32)
+    if n:
+        lib().isal_hip_ragged_items(int(ln.size), lp, tile, items.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)))
+    return items
+
+
+class Ragged:
+    """len(lens) stripes of one geometry, stripe s with shards of lens[s]
+    bytes, encoded or checked by one launch per pass (include/isal_hip.h
+    ragged batch).
+
+    data[s*k + j] / coding[s*rows + l] are addresses (or tensors) of 16-byte
+    aligned device buffers, as for Batch. encode() and check() only enqueue on
+    `stream`; check() fills the DEVICE buffer bad (one uint64 per stripe) as
+    Batch.check does, ~0 for a stripe of length 0."""
+
+    def __init__(self, k: int, rows: int, gftbls, lens: Sequence[int], data: Sequence, coding: Sequence):
+        ln = np.array(list(lens), dtype=np.int32)
+        nstripes = int(ln.size)
+        if len(data) != nstripes * k or len(coding) != nstripes * rows:
+            raise ValueError("pointer lists must hold len(lens)*k and len(lens)*rows entries")
+        h, bad = ctypes.c_void_p(), ctypes.c_int(-1)
+        rc = lib().isal_hip_ragged_create(ctypes.byref(h), k, rows, _p(gftbls), nstripes,
+                                          ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _pp(data), _pp(coding),
+                                          ctypes.byref(bad))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_ragged_create failed ({rc}, stripe {bad.value})")
+        self.k, self.rows, self.nstripes, self.lens = k, rows, nstripes, [int(x) for x in ln]
+        self._h = h
+
+    def encode(self, stream: int = 0) -> None:
+        rc = lib().isal_hip_ragged_encode(self._h, ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_ragged_encode failed ({rc})")
+
+    def check(self, bad, stream: int = 0) -> None:
+        rc = lib().isal_hip_ragged_check(self._h, ctypes.c_void_p(addr(bad)), ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_ragged_check failed ({rc})")
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().isal_hip_ragged_destroy(self._h)
             self._h = None
 
     def __del__(self):
