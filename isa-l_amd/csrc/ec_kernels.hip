@@ -62,6 +62,24 @@ struct EncOrder<2> {
   }
 };
 
+// One lane's 16 columns at off of one stripe (sp: its pointers, sources from
+// src0, outputs from dst0): the encode of every family. The kernels differ
+// only in where the stripe, the tile, len and tbl come from.
+template <int P, class Pol, int FL>
+__device__ __forceinline__ void encode_tile(const uint64_t* __restrict__ sp, int src0, int dst0,
+                                            const uint32_t* __restrict__ tbl, int k, long long off, int len,
+                                            unsigned long long r0m, unsigned c0m, const uint2* lt) {
+  if (off + kVec <= len) {
+    uint32_t acc[P][4];
+    accum16<P, Pol, FL>(acc, sp + src0, tbl, k, off, len, r0m, c0m, lt);
+#pragma unroll
+    for (int l = 0; l < P; ++l)
+      store16<Pol::ST>(sp[dst0 + l], off, make_uint4(acc[l][0], acc[l][1], acc[l][2], acc[l][3]), len);
+  } else if (off < len) {
+    dot_bytes<P>(sp, src0, dst0, tbl, k, off, static_cast<int>(len - off));
+  }
+}
+
 // The work items of an encode launch: (stripe, 4 KiB column tile) pairs.
 template <int P, class Pol, int FL, int B = kBlock>
 __device__ __forceinline__ void encode_items(const uint64_t* __restrict__ ptrs, int ptr_stride, int src0,
@@ -78,16 +96,7 @@ __device__ __forceinline__ void encode_items(const uint64_t* __restrict__ ptrs, 
     EncOrder<Pol::ORDER>::item(w, nitems, tiles, stripe, tile);
     const uint64_t* __restrict__ sp = ptrs + static_cast<size_t>(stripe) * ptr_stride;
     const long long off = static_cast<long long>(tile) * (B * kVec) + threadIdx.x * kVec;
-    if (off + kVec <= len) {
-      uint32_t acc[P][4];
-      accum16<P, Pol, FL>(acc, sp + src0, tbl, k, off, len, r0m, c0m, enc_lt);
-#pragma unroll
-      for (int l = 0; l < P; ++l)
-        store16<Pol::ST>(sp[dst0 + l], off, make_uint4(acc[l][0], acc[l][1], acc[l][2], acc[l][3]),
-                         len);
-    } else if (off < len) {
-      dot_bytes<P>(sp, src0, dst0, tbl, k, off, static_cast<int>(len - off));
-    }
+    encode_tile<P, Pol, FL>(sp, src0, dst0, tbl, k, off, len, r0m, c0m, enc_lt);
   }
 }
 
@@ -337,14 +346,8 @@ __global__ __launch_bounds__(kBlock, 4) void ec_encode_glds(const uint64_t* __re
 #pragma unroll
       for (int l = 0; l < P; ++l)
         store16<kBufNT>(sp[dst0 + l], off, make_uint4(acc[l][0], acc[l][1], acc[l][2], acc[l][3]), len);
-    } else if (off + kVec <= len) {
-      uint32_t acc[P][4];
-      accum16<P, EncPol<4, kBufNT, kBufNT, 2>, FL>(acc, sp + src0, tbl, k, off, len, r0m, c0m, lt);
-#pragma unroll
-      for (int l = 0; l < P; ++l)
-        store16<kBufNT>(sp[dst0 + l], off, make_uint4(acc[l][0], acc[l][1], acc[l][2], acc[l][3]), len);
-    } else if (off < len) {
-      dot_bytes<P>(sp, src0, dst0, tbl, k, off, static_cast<int>(len - off));
+    } else {
+      encode_tile<P, EncPol<4, kBufNT, kBufNT, 2>, FL>(sp, src0, dst0, tbl, k, off, len, r0m, c0m, lt);
     }
   }
 }
@@ -373,6 +376,16 @@ __global__ __launch_bounds__(kBlock) void ec_encode_b1(const uint64_t* __restric
 // call's device result word (kernel-argument launch). Nothing is written to
 // the shards.
 // ---------------------------------------------------------------------------
+// The verify family (verify_items, ec_verify_rag, ec_locate_v16) keeps its
+// tile body written out in each kernel. Shared as one verify_tile<P, Pol, FL>
+// with a sink per family (a row hook for the check, a whole-vector hook for
+// the locate), every one of the three lost occupancy or gained scratch
+// somewhere (VGPRs own -> shared): ec_verify_v16<5, EncPol<6, ..>, 0> 64 -> 72
+// and <6, EncPol<6, ..>, 0> 63 -> 71 (8 -> 7 waves per SIMD),
+// ec_verify_karg<8, EncPol<4, ..>, 1> and <8, EncPol<6, ..>, 1> 0 -> 20 bytes
+// of scratch, ec_verify_rag<5, EncPol<4, ..>> 64 -> 65 (8 -> 7),
+// ec_locate_v16<8, EncPol<4, ..>, 0> 96 -> 97 (5 -> 4). A change to the
+// kEarly rule or to the tail is made in all three.
 // sbad != nullptr (a batch): each stripe's mismatches lower sbad[stripe]
 // instead, and items run in the XCD-contiguous order of the encode.
 template <int P, class Pol, int FL>
@@ -894,6 +907,31 @@ __global__ __launch_bounds__(kBlock) void ec_encode_karg_ldsx(const isal_hip_kar
 // ---------------------------------------------------------------------------
 constexpr unsigned kMaxItems = 1u << 30;  // keep w / tiles in 32-bit scalar math
 
+unsigned tiles_of(int len, long long span) { return static_cast<unsigned>((len + span - 1) / span); }
+
+// Run-time value -> template argument: f(integral_constant<int, n>) for the n
+// of N... that equals v; false (f not called) when none does.
+template <int... N, class F>
+bool dispatch(int v, F&& f) {
+  return ((v == N && (f(std::integral_constant<int, N>{}), true)) || ...);
+}
+
+// The rows of a pass, 1 .. EC_MAX_ROWS_PER_PASS
+template <class F>
+bool with_rows(int P, F&& f) {
+  static_assert(EC_MAX_ROWS_PER_PASS == 8, "one kernel per row count of a pass");
+  return dispatch<1, 2, 3, 4, 5, 6, 7, 8>(P, f);
+}
+
+// The 0/1 form (isal_hip_encmask) or the plain lookup
+template <class F>
+void with_xor(bool x, F&& f) {
+  if (x)
+    f(std::integral_constant<int, kEncXor>{});
+  else
+    f(std::integral_constant<int, kEncLUT>{});
+}
+
 // One workgroup per item. (A capped grid striding over the items lost 13-20 %
 // on C2 at 2048-16384 workgroups, profiles/r04_ldsmin_ab.jsonl; the knob that
 // chose it was removed in round 5.)
@@ -962,6 +1000,12 @@ int enc_group(int k, int P = 0) {
   return 4;
 }
 
+// enc_group's candidates; anything else takes the groups of 4, its fallback
+template <class F>
+void with_enc_group(int k, int P, F&& f) {
+  if (!dispatch<12, 10, 8, 6, 5>(enc_group(k, P), f)) f(std::integral_constant<int, 4>{});
+}
+
 // Low table halves from LDS (kEncLds). Same-box A/B, two runs each
 // (profiles/r04_lds_ab.jsonl, with the XOR path): k20p6 0.635 -> 0.663 of
 // 8 TB/s, k10p6 0.752 -> 0.754, C2 0.7705 -> 0.7695, k10p8 0.715 -> 0.702,
@@ -1027,7 +1071,7 @@ void launch_fl(hipStream_t s, const uint64_t* ptrs, int ptr_stride, int src0, in
                int len, int k, unsigned nstripes, unsigned long long r0m, unsigned c0m) {
   constexpr int B = enc_block<P>();
   log_launch<P, EncPol<U, kBufNT, kBufNT, 2>, FL, B>();
-  const unsigned tiles = static_cast<unsigned>((static_cast<long long>(len) + B * kVec - 1) / (B * kVec));
+  const unsigned tiles = tiles_of(len, B * kVec);
   const unsigned nitems = nstripes * tiles;
   const size_t lds = enc_lds_alloc((FL & kEncLds) ? lds_bytes<P>(k) : 0, P);
   ISAL_LAUNCH((ec_encode_v16<P, EncPol<U, kBufNT, kBufNT, 2>, FL, B>), dim3(grid_for(nitems)), dim3(B), lds, s,
@@ -1088,11 +1132,10 @@ void launch_ldsx(unsigned grid, hipStream_t s, const uint64_t* ptrs, int ptr_str
 }
 
 template <int P>
-hipError_t encode_pass(const uint64_t* ptrs, int ptr_stride, int src0, int dst0, const uint32_t* tbl,
-                       const uint64_t* ldsx, int len, int k, unsigned nstripes, bool vec16, bool x,
-                       unsigned long long r0m, unsigned c0m, hipStream_t s) {
-  const unsigned span = vec16 ? kTile : kBlock;
-  const unsigned tiles = static_cast<unsigned>((static_cast<long long>(len) + span - 1) / span);
+void encode_pass(const uint64_t* ptrs, int ptr_stride, int src0, int dst0, const uint32_t* tbl,
+                 const uint64_t* ldsx, int len, int k, unsigned nstripes, bool vec16, bool x,
+                 unsigned long long r0m, unsigned c0m, hipStream_t s) {
+  const unsigned tiles = tiles_of(len, vec16 ? kTile : kBlock);
   const unsigned nitems = nstripes * tiles;
   const unsigned grid = grid_for(nitems);
   if (vec16 && enc_ldsx(P, k, ldsx)) {
@@ -1102,21 +1145,13 @@ hipError_t encode_pass(const uint64_t* ptrs, int ptr_stride, int src0, int dst0,
   } else if (vec16 && enc_glds(P)) {
     launch_glds_r<P>(x, grid, s, ptrs, ptr_stride, src0, dst0, tbl, len, k, nitems, tiles, r0m, c0m);
   } else if (vec16) {
-    switch (enc_group(k, P)) {
-#define EC_GROUP(u)                                                                          \
-  case u:                                                                                    \
-    launch_v16<P, u>(s, ptrs, ptr_stride, src0, dst0, tbl, len, k, nstripes, x, r0m, c0m);  \
-    break;
-      EC_GROUP(12) EC_GROUP(10) EC_GROUP(8) EC_GROUP(6) EC_GROUP(5)
-#undef EC_GROUP
-      default: launch_v16<P, 4>(s, ptrs, ptr_stride, src0, dst0, tbl, len, k, nstripes, x, r0m, c0m); break;
-    }
+    with_enc_group(k, P, [&](auto u) {
+      launch_v16<P, decltype(u)::value>(s, ptrs, ptr_stride, src0, dst0, tbl, len, k, nstripes, x, r0m, c0m);
+    });
   } else {
     ISAL_LAUNCH(ec_encode_b1<P>, dim3(grid), dim3(kBlock), 0, s, ptrs, ptr_stride, src0,
                        dst0, tbl, len, k, nitems, tiles);
   }
-  isal_hip_count_launch();
-  return hipGetLastError();
 }
 
 // The device update runs 128-lane workgroups (2 KiB tiles): C4 shape (k20 p6,
@@ -1128,24 +1163,20 @@ hipError_t encode_pass(const uint64_t* ptrs, int ptr_stride, int src0, int dst0,
 constexpr int kUpdBlock = 128, kUpdTile = kUpdBlock * kVec;
 
 template <int P>
-hipError_t update_pass(const uint64_t* ptrs, int ptr_stride, int src_idx, int dst0,
-                       const uint32_t* tbl, int len, unsigned nstripes, bool vec16, hipStream_t s) {
-  const unsigned span = vec16 ? kTile : kBlock;
-  const unsigned tiles = static_cast<unsigned>((static_cast<long long>(len) + span - 1) / span);
+void update_pass(const uint64_t* ptrs, int ptr_stride, int src_idx, int dst0, const uint32_t* tbl, int len,
+                 unsigned nstripes, bool vec16, hipStream_t s) {
+  // 128-lane workgroups, 2 KiB column tiles (kUpdBlock); the caller splits
+  // launches with stripes_per_launch(len, true, kUpdTile)
+  const unsigned tiles = tiles_of(len, vec16 ? kUpdTile : kBlock);
   const unsigned nitems = nstripes * tiles;
   // (An occupancy cap through dynamic LDS measured flat at 8 workgroups per
   // CU and 2-9 % slower at 4-6, profiles/r04_update_occupancy_ab.jsonl.)
-  if (vec16) {
-    // 128-lane workgroups, 2 KiB column tiles (kUpdBlock); the caller splits
-    // launches with stripes_per_launch(len, true, kUpdTile)
-    const unsigned t2 = static_cast<unsigned>((static_cast<long long>(len) + kUpdTile - 1) / kUpdTile);
-    ISAL_LAUNCH((ec_update_v16<P, kUpdBlock>), dim3(grid_for(nstripes * t2)), dim3(kUpdBlock), 0, s, ptrs,
-                ptr_stride, src_idx, dst0, tbl, len, nstripes * t2, t2);
-  } else
+  if (vec16)
+    ISAL_LAUNCH((ec_update_v16<P, kUpdBlock>), dim3(grid_for(nitems)), dim3(kUpdBlock), 0, s, ptrs, ptr_stride,
+                src_idx, dst0, tbl, len, nitems, tiles);
+  else
     ISAL_LAUNCH(ec_update_b1<P>, dim3(grid_for(nitems)), dim3(kBlock), 0, s, ptrs,
                        ptr_stride, src_idx, dst0, tbl, len, nitems, tiles);
-  isal_hip_count_launch();
-  return hipGetLastError();
 }
 
 // Largest stripe count per launch so that nitems stays below kMaxItems.
@@ -1154,6 +1185,62 @@ unsigned stripes_per_launch(int len, bool vec16, long long vspan = kTile) {
   const long long tiles = (static_cast<long long>(len) + span - 1) / span;
   const long long n = static_cast<long long>(kMaxItems) / (tiles ? tiles : 1);
   return static_cast<unsigned>(n > 0 ? n : 1);
+}
+
+// f(s0, ns, ptrs) for every slice [s0, s0 + ns) of at most `per` stripes, ptrs
+// = the slice's rows of the pointer table; stops at f's first error.
+template <class F>
+hipError_t for_slices(const uint64_t* d_ptrs, int ptr_stride, long long nstripes, unsigned per, F&& f) {
+  for (long long s0 = 0; s0 < nstripes; s0 += per) {
+    const unsigned ns = static_cast<unsigned>(nstripes - s0 < per ? nstripes - s0 : per);
+    const hipError_t e = f(s0, ns, d_ptrs + s0 * ptr_stride);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// The 0/1 masks of a call, or none under ISAL_HIP_ENC_XOR=0 (read at launch,
+// so handles created before isal_hip_config_reload() follow it too).
+const isal_hip_encmask* enc_xor_masks(const isal_hip_encmask* em) {
+  return isal_hip_knob(ISAL_HIP_KNOB_ENC_XOR) == 0 ? nullptr : em;
+}
+
+// The 0/1 form of pass g of a call: x = it has one, else all zero.
+struct PassMask {
+  bool x;
+  unsigned long long r0m;
+  unsigned c0m;
+};
+
+PassMask pass_mask(const isal_hip_encmask* em, int g) {
+  em = enc_xor_masks(em);
+  if (!em || g >= EC_MAX_PASSES || !((em->ok >> g) & 1u)) return {false, 0ull, 0u};
+  return {true, em->r0[g], em->c0[g]};
+}
+
+// One pass of a launch: rows [r0, r0 + P) of the matrix, the g-th pass, with
+// its [k][P] coefficient tables and its 0/1 form.
+struct Pass {
+  int r0, P, g;
+  const uint32_t* tbl;
+  PassMask m;
+};
+
+// f(pass) launches one kernel for each pass of `rows` rows, or returns an
+// error without launching; every launch is counted and checked. Stops at the
+// first error.
+template <class F>
+hipError_t for_passes(const uint32_t* d_tbl, int k, int rows, const isal_hip_encmask* em, F&& f) {
+  for (int r0 = 0; r0 < rows; r0 += EC_MAX_ROWS_PER_PASS) {
+    const int P = rows - r0 < EC_MAX_ROWS_PER_PASS ? rows - r0 : EC_MAX_ROWS_PER_PASS;
+    const int g = r0 / EC_MAX_ROWS_PER_PASS;
+    hipError_t e = f(Pass{r0, P, g, d_tbl + static_cast<size_t>(kTbl) * k * r0, pass_mask(em, g)});
+    if (e != hipSuccess) return e;
+    isal_hip_count_launch();
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 // ---------------------------------------------------------------------------
@@ -1179,14 +1266,24 @@ __global__ __launch_bounds__(B, (enc_waves<P, Pol::U, kEncLUT>())) void ec_repai
     const unsigned p = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(pat[row])));
     const uint32_t* __restrict__ tbl = tbl0 + static_cast<size_t>(p) * tbl_stride;
     const long long off = static_cast<long long>(tile) * (B * kVec) + threadIdx.x * kVec;
-    if (off + kVec <= len) {
-      uint32_t acc[P][4];
-      accum16<P, Pol, kEncLUT>(acc, sp, tbl, k, off, len);
+    if constexpr ((P == 7 && Pol::U == 4) || (P == 3 && Pol::U == 10)) {
+      // Two instantiations keep encode_tile's body written out. Through the
+      // call ec_repair_v16<7, EncPol<4, ..>, 256> takes 92 VGPRs instead of
+      // 79, a wave per SIMD less; ec_repair_v16<3, EncPol<10, ..>, 256> (rs
+      // 10+4, three erasures) takes 72 instead of 73 but measured 2.2400 ms
+      // against the parent's 2.2281-2.2378 on 64 KiB x 16384 stripes of one
+      // pattern (profiles/refactor_tiles_ab.jsonl, run 2).
+      if (off + kVec <= len) {
+        uint32_t acc[P][4];
+        accum16<P, Pol, kEncLUT>(acc, sp, tbl, k, off, len);
 #pragma unroll
-      for (int l = 0; l < P; ++l)
-        store16<Pol::ST>(sp[dst0 + l], off, make_uint4(acc[l][0], acc[l][1], acc[l][2], acc[l][3]), len);
-    } else if (off < len) {
-      dot_bytes<P>(sp, 0, dst0, tbl, k, off, static_cast<int>(len - off));
+        for (int l = 0; l < P; ++l)
+          store16<Pol::ST>(sp[dst0 + l], off, make_uint4(acc[l][0], acc[l][1], acc[l][2], acc[l][3]), len);
+      } else if (off < len) {
+        dot_bytes<P>(sp, 0, dst0, tbl, k, off, static_cast<int>(len - off));
+      }
+    } else {
+      encode_tile<P, Pol, kEncLUT>(sp, 0, dst0, tbl, k, off, len, 0ull, 0u, nullptr);
     }
   }
 }
@@ -1199,26 +1296,10 @@ void launch_repair(hipStream_t s, const uint64_t* ptrs, int ptr_stride, const ui
                    unsigned tbl_stride, int dst0, int len, int k, unsigned nrows) {
   constexpr int B = enc_block<P>();
   if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2) fprintf(stderr, "isal_hip: kernel ec_repair_v16<%d, %d, %d>\n", P, U, B);
-  const unsigned tiles = static_cast<unsigned>((static_cast<long long>(len) + B * kVec - 1) / (B * kVec));
+  const unsigned tiles = tiles_of(len, B * kVec);
   const unsigned nitems = nrows * tiles;
   ISAL_LAUNCH((ec_repair_v16<P, EncPol<U, kBufNT, kBufNT, 2>, B>), dim3(grid_for(nitems)), dim3(B),
               enc_lds_alloc(0, P), s, ptrs, ptr_stride, pat, tbl0, tbl_stride, dst0, len, k, nitems, tiles);
-}
-
-template <int P>
-hipError_t repair_pass(hipStream_t s, const uint64_t* ptrs, int ptr_stride, const uint32_t* pat, const uint32_t* tbl0,
-                       unsigned tbl_stride, int dst0, int len, int k, unsigned nrows) {
-  switch (enc_group(k, P)) {
-#define EC_GROUP(u)                                                                          \
-  case u:                                                                                    \
-    launch_repair<P, u>(s, ptrs, ptr_stride, pat, tbl0, tbl_stride, dst0, len, k, nrows);   \
-    break;
-    EC_GROUP(12) EC_GROUP(10) EC_GROUP(8) EC_GROUP(6) EC_GROUP(5)
-#undef EC_GROUP
-    default: launch_repair<P, 4>(s, ptrs, ptr_stride, pat, tbl0, tbl_stride, dst0, len, k, nrows); break;
-  }
-  isal_hip_count_launch();
-  return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------
@@ -1247,8 +1328,8 @@ __device__ __forceinline__ RagItem rag_item(const uint2* __restrict__ items, con
   return r;
 }
 
-// encode_items' body for one item: sources at [0, k), outputs at [dst0, dst0 + P)
-// of the stripe's pointers.
+// The encode of one item: sources at [0, k), outputs at [dst0, dst0 + P) of
+// the stripe's pointers.
 template <int P, class Pol, int B>
 __global__ __launch_bounds__(B, (enc_waves<P, Pol::U, kEncLUT>())) void ec_encode_rag(
     const uint64_t* __restrict__ ptrs, int ptr_stride, const uint2* __restrict__ items,
@@ -1256,16 +1337,24 @@ __global__ __launch_bounds__(B, (enc_waves<P, Pol::U, kEncLUT>())) void ec_encod
   if (blockIdx.x >= nitems) return;
   const RagItem it = rag_item(items, lens, nitems);
   const uint64_t* __restrict__ sp = ptrs + static_cast<size_t>(it.stripe) * ptr_stride;
-  const int len = it.len;
   const long long off = static_cast<long long>(it.tile) * (B * kVec) + threadIdx.x * kVec;
-  if (off + kVec <= len) {
-    uint32_t acc[P][4];
-    accum16<P, Pol, kEncLUT>(acc, sp, tbl, k, off, len);
+  if constexpr ((P == 7 && Pol::U == 4) || (P == 4 && Pol::U == 8)) {
+    // ec_encode_rag<7, EncPol<4, ..>, 256> and <4, EncPol<8, ..>, 256> keep
+    // encode_tile's body written out: through the call they take 90 VGPRs
+    // instead of 78 and 73 instead of 72, each a wave per SIMD less
+    // (profiles/refactor_tiles_resources_*.tsv).
+    const int len = it.len;
+    if (off + kVec <= len) {
+      uint32_t acc[P][4];
+      accum16<P, Pol, kEncLUT>(acc, sp, tbl, k, off, len);
 #pragma unroll
-    for (int l = 0; l < P; ++l)
-      store16<Pol::ST>(sp[dst0 + l], off, make_uint4(acc[l][0], acc[l][1], acc[l][2], acc[l][3]), len);
-  } else if (off < len) {
-    dot_bytes<P>(sp, 0, dst0, tbl, k, off, static_cast<int>(len - off));
+      for (int l = 0; l < P; ++l)
+        store16<Pol::ST>(sp[dst0 + l], off, make_uint4(acc[l][0], acc[l][1], acc[l][2], acc[l][3]), len);
+    } else if (off < len) {
+      dot_bytes<P>(sp, 0, dst0, tbl, k, off, static_cast<int>(len - off));
+    }
+  } else {
+    encode_tile<P, Pol, kEncLUT>(sp, 0, dst0, tbl, k, off, it.len, 0ull, 0u, nullptr);
   }
 }
 
@@ -1325,22 +1414,6 @@ void launch_encode_rag(hipStream_t s, const uint64_t* ptrs, int ptr_stride, cons
   if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2) fprintf(stderr, "isal_hip: kernel ec_encode_rag<%d, %d, %d>\n", P, U, B);
   ISAL_LAUNCH((ec_encode_rag<P, EncPol<U, kBufNT, kBufNT, 2>, B>), dim3(grid_for(nitems)), dim3(B),
               enc_lds_alloc(0, P), s, ptrs, ptr_stride, items, lens, tbl, dst0, k, nitems);
-}
-
-template <int P>
-hipError_t encode_rag_pass(hipStream_t s, const uint64_t* ptrs, int ptr_stride, const uint2* items, const int* lens,
-                           const uint32_t* tbl, int dst0, int k, unsigned nitems) {
-  switch (enc_group(k, P)) {
-#define EC_GROUP(u)                                                                  \
-  case u:                                                                            \
-    launch_encode_rag<P, u>(s, ptrs, ptr_stride, items, lens, tbl, dst0, k, nitems); \
-    break;
-    EC_GROUP(12) EC_GROUP(10) EC_GROUP(8) EC_GROUP(6) EC_GROUP(5)
-#undef EC_GROUP
-    default: launch_encode_rag<P, 4>(s, ptrs, ptr_stride, items, lens, tbl, dst0, k, nitems); break;
-  }
-  isal_hip_count_launch();
-  return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------
@@ -1450,9 +1523,9 @@ __global__ __launch_bounds__(B) void ec_overwrite_v16(const uint64_t* __restrict
 // One pass of P rows over nstripes table rows: the update kernel's 128-lane
 // workgroups and 2 KiB column tiles (kUpdBlock).
 template <int P>
-hipError_t overwrite_pass(hipStream_t s, const uint64_t* ptrs, int ptr_stride, const uint32_t* idx,
-                          const uint32_t* tbl0, int nw, int dst0, int len, unsigned nstripes, bool commit) {
-  const unsigned tiles = static_cast<unsigned>((static_cast<long long>(len) + kUpdTile - 1) / kUpdTile);
+void overwrite_pass(hipStream_t s, const uint64_t* ptrs, int ptr_stride, const uint32_t* idx, const uint32_t* tbl0,
+                    int nw, int dst0, int len, unsigned nstripes, bool commit) {
+  const unsigned tiles = tiles_of(len, kUpdTile);
   const unsigned nitems = nstripes * tiles;
   if (commit)
     ISAL_LAUNCH((ec_overwrite_v16<P, true, kUpdBlock>), dim3(grid_for(nitems)), dim3(kUpdBlock), 0, s, ptrs,
@@ -1460,17 +1533,9 @@ hipError_t overwrite_pass(hipStream_t s, const uint64_t* ptrs, int ptr_stride, c
   else
     ISAL_LAUNCH((ec_overwrite_v16<P, false, kUpdBlock>), dim3(grid_for(nitems)), dim3(kUpdBlock), 0, s, ptrs,
                 ptr_stride, idx, tbl0, nw, dst0, len, nitems, tiles);
-  isal_hip_count_launch();
-  return hipGetLastError();
 }
 
 }  // namespace
-
-// The 0/1 masks of a call, or none under ISAL_HIP_ENC_XOR=0 (read at launch,
-// so handles created before isal_hip_config_reload() follow it too).
-static const isal_hip_encmask* enc_xor_masks(const isal_hip_encmask* em) {
-  return isal_hip_knob(ISAL_HIP_KNOB_ENC_XOR) == 0 ? nullptr : em;
-}
 
 extern "C" int isal_hip_launch_encode(const uint64_t* d_ptrs, int ptr_stride, int src_idx0,
                                       int dst_idx0, const uint32_t* d_tbl, int len, int k, int rows,
@@ -1479,34 +1544,19 @@ extern "C" int isal_hip_launch_encode(const uint64_t* d_ptrs, int ptr_stride, in
   if (len <= 0 || rows <= 0 || nstripes <= 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint64_t* ldsx_all = em ? em->ldsx : nullptr;
-  em = enc_xor_masks(em);
-  const unsigned per = stripes_per_launch(len, vec16 != 0, kEncMinSpan);
-  for (long long s0 = 0; s0 < nstripes; s0 += per) {
-    const unsigned ns = static_cast<unsigned>(nstripes - s0 < per ? nstripes - s0 : per);
-    const uint64_t* ptrs = d_ptrs + s0 * ptr_stride;
-    for (int r0 = 0; r0 < rows; r0 += EC_MAX_ROWS_PER_PASS) {
-      const int P = rows - r0 < EC_MAX_ROWS_PER_PASS ? rows - r0 : EC_MAX_ROWS_PER_PASS;
-      const uint32_t* tbl = d_tbl + static_cast<size_t>(kTbl) * k * r0;
-      const uint64_t* ldsx =
-          ldsx_all ? ldsx_all + static_cast<size_t>(r0 / EC_MAX_ROWS_PER_PASS) * k * ISAL_HIP_LDSX_ENTRIES : nullptr;
-      const int dst0 = dst_idx0 + r0;
-      const int g = r0 / EC_MAX_ROWS_PER_PASS;
-      const bool x = em && g < EC_MAX_PASSES && ((em->ok >> g) & 1u);
-      const unsigned long long r0m = x ? em->r0[g] : 0ull;
-      const unsigned c0m = x ? em->c0[g] : 0u;
-      hipError_t e = hipSuccess;
-      switch (P) {
-#define EC_CASE(n)                                                                                      \
-  case n:                                                                                               \
-    e = encode_pass<n>(ptrs, ptr_stride, src_idx0, dst0, tbl, ldsx, len, k, ns, vec16 != 0, x, r0m, c0m, s); \
-    break;
-        EC_CASE(1) EC_CASE(2) EC_CASE(3) EC_CASE(4) EC_CASE(5) EC_CASE(6) EC_CASE(7) EC_CASE(8)
-#undef EC_CASE
-      }
-      if (e != hipSuccess) return static_cast<int>(e);
-    }
-  }
-  return 0;
+  return for_slices(
+      d_ptrs, ptr_stride, nstripes, stripes_per_launch(len, vec16 != 0, kEncMinSpan),
+      [&](long long, unsigned ns, const uint64_t* ptrs) {
+        return for_passes(d_tbl, k, rows, em, [&](const Pass& p) {
+          const uint64_t* ldsx =
+              ldsx_all ? ldsx_all + static_cast<size_t>(p.g) * k * ISAL_HIP_LDSX_ENTRIES : nullptr;
+          with_rows(p.P, [&](auto P) {
+            encode_pass<decltype(P)::value>(ptrs, ptr_stride, src_idx0, dst_idx0 + p.r0, p.tbl, ldsx, len, k, ns,
+                                            vec16 != 0, p.m.x, p.m.r0m, p.m.c0m, s);
+          });
+          return hipSuccess;
+        });
+      });
 }
 
 extern "C" int isal_hip_launch_repair(const uint64_t* d_ptrs, int ptr_stride, const uint32_t* d_pat,
@@ -1514,26 +1564,18 @@ extern "C" int isal_hip_launch_repair(const uint64_t* d_ptrs, int ptr_stride, co
                                       long long nrows, void* stream) {
   if (len <= 0 || rows <= 0 || nrows <= 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const unsigned per = stripes_per_launch(len, true, kEncMinSpan);
-  for (long long s0 = 0; s0 < nrows; s0 += per) {
-    const unsigned ns = static_cast<unsigned>(nrows - s0 < per ? nrows - s0 : per);
-    const uint64_t* ptrs = d_ptrs + s0 * ptr_stride;
-    for (int r0 = 0; r0 < rows; r0 += EC_MAX_ROWS_PER_PASS) {
-      const int P = rows - r0 < EC_MAX_ROWS_PER_PASS ? rows - r0 : EC_MAX_ROWS_PER_PASS;
-      const uint32_t* tbl0 = d_tbl + static_cast<size_t>(kTbl) * k * r0;
-      hipError_t e = hipSuccess;
-      switch (P) {
-#define EC_CASE(n)                                                                                   \
-  case n:                                                                                            \
-    e = repair_pass<n>(s, ptrs, ptr_stride, d_pat + s0, tbl0, tbl_stride, k + r0, len, k, ns);       \
-    break;
-        EC_CASE(1) EC_CASE(2) EC_CASE(3) EC_CASE(4) EC_CASE(5) EC_CASE(6) EC_CASE(7) EC_CASE(8)
-#undef EC_CASE
-      }
-      if (e != hipSuccess) return static_cast<int>(e);
-    }
-  }
-  return 0;
+  return for_slices(d_ptrs, ptr_stride, nrows, stripes_per_launch(len, true, kEncMinSpan),
+                    [&](long long s0, unsigned ns, const uint64_t* ptrs) {
+                      return for_passes(d_tbl, k, rows, nullptr, [&](const Pass& p) {
+                        with_rows(p.P, [&](auto P) {
+                          with_enc_group(k, p.P, [&](auto u) {
+                            launch_repair<decltype(P)::value, decltype(u)::value>(
+                                s, ptrs, ptr_stride, d_pat + s0, p.tbl, tbl_stride, k + p.r0, len, k, ns);
+                          });
+                        });
+                        return hipSuccess;
+                      });
+                    });
 }
 
 extern "C" int isal_hip_launch_overwrite(const uint64_t* d_ptrs, int ptr_stride, const uint32_t* d_idx,
@@ -1541,29 +1583,18 @@ extern "C" int isal_hip_launch_overwrite(const uint64_t* d_ptrs, int ptr_stride,
                                          long long nstripes, int commit, void* stream) {
   if (len <= 0 || rows <= 0 || nw <= 0 || nstripes <= 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const unsigned per = stripes_per_launch(len, true, kUpdTile);
-  for (long long s0 = 0; s0 < nstripes; s0 += per) {
-    const unsigned ns = static_cast<unsigned>(nstripes - s0 < per ? nstripes - s0 : per);
-    const uint64_t* ptrs = d_ptrs + s0 * ptr_stride;
-    const uint32_t* idx = d_idx + s0 * nw;
-    for (int r0 = 0; r0 < rows; r0 += EC_MAX_ROWS_PER_PASS) {
-      const int P = rows - r0 < EC_MAX_ROWS_PER_PASS ? rows - r0 : EC_MAX_ROWS_PER_PASS;
-      const uint32_t* tbl0 = d_tbl + static_cast<size_t>(kTbl) * k * r0;
-      // new goes over old only once every row of the stripe has seen the delta
-      const bool last = commit && r0 + P == rows;
-      hipError_t e = hipSuccess;
-      switch (P) {
-#define EC_CASE(n)                                                                          \
-  case n:                                                                                   \
-    e = overwrite_pass<n>(s, ptrs, ptr_stride, idx, tbl0, nw, 2 * nw + r0, len, ns, last); \
-    break;
-        EC_CASE(1) EC_CASE(2) EC_CASE(3) EC_CASE(4) EC_CASE(5) EC_CASE(6) EC_CASE(7) EC_CASE(8)
-#undef EC_CASE
-      }
-      if (e != hipSuccess) return static_cast<int>(e);
-    }
-  }
-  return 0;
+  return for_slices(d_ptrs, ptr_stride, nstripes, stripes_per_launch(len, true, kUpdTile),
+                    [&](long long s0, unsigned ns, const uint64_t* ptrs) {
+                      return for_passes(d_tbl, k, rows, nullptr, [&](const Pass& p) {
+                        // new goes over old only once every row of the stripe has seen the delta
+                        const bool last = commit && p.r0 + p.P == rows;
+                        with_rows(p.P, [&](auto P) {
+                          overwrite_pass<decltype(P)::value>(s, ptrs, ptr_stride, d_idx + s0 * nw, p.tbl, nw,
+                                                             2 * nw + p.r0, len, ns, last);
+                        });
+                        return hipSuccess;
+                      });
+                    });
 }
 
 // ISAL_HIP_KARG_NARROW: 1 = always the 4-byte-lane kernel, 0 = never;
@@ -1614,7 +1645,7 @@ extern "C" int isal_hip_launch_encode_karg(const isal_hip_karg* a, const isal_hi
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool narrow = karg_narrow(len, busy);
   if (!narrow && isal_hip_karg_ldsx(k, rows) && ldsx) {  // 16-byte lanes on the product tables
-    const unsigned tiles = static_cast<unsigned>((static_cast<long long>(len) + kTile - 1) / kTile);
+    const unsigned tiles = tiles_of(len, kTile);
     const size_t lds = static_cast<size_t>(k) * ISAL_HIP_LDSX_ENTRIES * 8;
     if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2) fprintf(stderr, "isal_hip: kernel ec_encode_karg_ldsx<%d>\n", rows);
     switch (rows) {
@@ -1629,40 +1660,26 @@ extern "C" int isal_hip_launch_encode_karg(const isal_hip_karg* a, const isal_hi
   if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2)
     fprintf(stderr, "isal_hip: kernel %s<%d>\n", narrow ? "ec_encode_karg4" : "ec_encode_karg", rows);
   if (narrow) {
-    const unsigned blocks = static_cast<unsigned>((static_cast<long long>(len) + 4 * kBlock - 1) / (4 * kBlock));
-    switch (rows) {
-#define EC_KARG4(n)                                                                                           \
-  case n:                                                                                                     \
-    ISAL_LAUNCH((ec_encode_karg4<n>), dim3(blocks), dim3(kBlock), 0, s, *a, *d, len, k);              \
-    break;
-      EC_KARG4(1) EC_KARG4(2) EC_KARG4(3) EC_KARG4(4) EC_KARG4(5) EC_KARG4(6) EC_KARG4(7) EC_KARG4(8)
-#undef EC_KARG4
-      default: return static_cast<int>(hipErrorInvalidValue);
-    }
+    const unsigned blocks = tiles_of(len, 4 * kBlock);
+    if (!with_rows(rows, [&](auto P) {
+          ISAL_LAUNCH((ec_encode_karg4<decltype(P)::value>), dim3(blocks), dim3(kBlock), 0, s, *a, *d, len, k);
+        }))
+      return static_cast<int>(hipErrorInvalidValue);
     isal_hip_count_launch();
     return static_cast<int>(hipGetLastError());
   }
-  const unsigned tiles = static_cast<unsigned>((static_cast<long long>(len) + kTile - 1) / kTile);
-  em = enc_xor_masks(em);
-  const bool x = em && (em->ok & 1u);
-  const unsigned long long r0m = x ? em->r0[0] : 0ull;
-  const unsigned c0m = x ? em->c0[0] : 0u;
-  switch (rows * 16 + enc_group(k)) {
-#define EC_KARG(n, u)                                                                                   \
-  case n * 16 + u:                                                                                      \
-    if (x)                                                                                              \
-      ISAL_LAUNCH((ec_encode_karg<n, EncPol<u, kBufNT, kBufSC1NT, 2>, kEncXor>), dim3(tiles),      \
-                         dim3(kBlock), 0, s, *a, *d, len, k, tiles, r0m, c0m);                          \
-    else                                                                                                \
-      ISAL_LAUNCH((ec_encode_karg<n, EncPol<u, kBufNT, kBufSC1NT, 2>, kEncLUT>), dim3(tiles),      \
-                         dim3(kBlock), 0, s, *a, *d, len, k, tiles, 0ull, 0u);                          \
-    break;
-#define EC_KARG_U(n) EC_KARG(n, 12) EC_KARG(n, 10) EC_KARG(n, 8) EC_KARG(n, 6) EC_KARG(n, 5) EC_KARG(n, 4)
-    EC_KARG_U(1) EC_KARG_U(2) EC_KARG_U(3) EC_KARG_U(4) EC_KARG_U(5) EC_KARG_U(6) EC_KARG_U(7) EC_KARG_U(8)
-#undef EC_KARG_U
-#undef EC_KARG
-    default: return static_cast<int>(hipErrorInvalidValue);
-  }
+  const unsigned tiles = tiles_of(len, kTile);
+  const PassMask m = pass_mask(em, 0);
+  const bool launched = with_rows(rows, [&](auto P) {
+    with_enc_group(k, 0, [&](auto u) {
+      with_xor(m.x, [&](auto fl) {
+        ISAL_LAUNCH((ec_encode_karg<decltype(P)::value, EncPol<decltype(u)::value, kBufNT, kBufSC1NT, 2>,
+                                    decltype(fl)::value>),
+                    dim3(tiles), dim3(kBlock), 0, s, *a, *d, len, k, tiles, m.r0m, m.c0m);
+      });
+    });
+  });
+  if (!launched) return static_cast<int>(hipErrorInvalidValue);
   isal_hip_count_launch();
   return static_cast<int>(hipGetLastError());
 }
@@ -1673,15 +1690,10 @@ extern "C" int isal_hip_launch_update_karg(const isal_hip_karg* a, const isal_hi
   if (!d) d = &kNoDone;
   if (rows > EC_MAX_ROWS_PER_PASS) return static_cast<int>(hipErrorInvalidValue);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const unsigned tiles = static_cast<unsigned>((static_cast<long long>(len) + kTile - 1) / kTile);
-  switch (rows) {
-#define EC_UKARG(n)                                                                                   \
-  case n:                                                                                             \
-    ISAL_LAUNCH(ec_update_karg<n>, dim3(tiles), dim3(kBlock), 0, s, *a, *d, len, tiles);       \
-    break;
-    EC_UKARG(1) EC_UKARG(2) EC_UKARG(3) EC_UKARG(4) EC_UKARG(5) EC_UKARG(6) EC_UKARG(7) EC_UKARG(8)
-#undef EC_UKARG
-  }
+  const unsigned tiles = tiles_of(len, kTile);
+  with_rows(rows, [&](auto P) {
+    ISAL_LAUNCH(ec_update_karg<decltype(P)::value>, dim3(tiles), dim3(kBlock), 0, s, *a, *d, len, tiles);
+  });
   isal_hip_count_launch();
   return static_cast<int>(hipGetLastError());
 }
@@ -1696,34 +1708,30 @@ static int verify_group(int k) {
   return 4;
 }
 
-template <int P, int U, int FL>
-void launch_verify_v16(unsigned grid, hipStream_t s, const uint64_t* d_ptrs, int ptr_stride, int src_idx0, int dst0,
-                       const uint32_t* tbl, int len, int k, unsigned nitems, unsigned tiles, unsigned long long* out,
-                       int r0, long long col0, unsigned long long r0m, unsigned c0m, unsigned long long* sbad) {
-  ISAL_LAUNCH((ec_verify_v16<P, EncPol<U, kBufNT, kBufNT, 0>, FL>), dim3(grid), dim3(kBlock), 0, s, d_ptrs,
-                     ptr_stride, src_idx0, dst0, tbl, len, k, nitems, tiles, out, r0, col0, r0m, c0m, sbad);
+// verify_group's candidates; anything else takes the groups of 4, its fallback
+template <class F>
+static void with_verify_group(int k, F&& f) {
+  if (!dispatch<10, 8, 6>(verify_group(k), f)) f(std::integral_constant<int, 4>{});
 }
 
-// One pass of the 16-byte verify (P rows from r0) over nstripes stripes.
-static void verify_pass_v16(int P, int U, bool x, unsigned grid, hipStream_t s, const uint64_t* d_ptrs,
-                            int ptr_stride, int src_idx0, int dst0, const uint32_t* tbl, int len, int k,
-                            unsigned nitems, unsigned tiles, unsigned long long* out, int r0, long long col0,
-                            unsigned long long r0m, unsigned c0m, unsigned long long* sbad) {
-  switch (P * 64 + U * 2 + (x ? 1 : 0)) {
-#define EC_VCASE(n, u)                                                                                          \
-  case n * 64 + u * 2:                                                                                          \
-    launch_verify_v16<n, u, kEncLUT>(grid, s, d_ptrs, ptr_stride, src_idx0, dst0, tbl, len, k, nitems, tiles, out, \
-                                     r0, col0, 0ull, 0u, sbad);                                                 \
-    break;                                                                                                      \
-  case n * 64 + u * 2 + 1:                                                                                      \
-    launch_verify_v16<n, u, kEncXor>(grid, s, d_ptrs, ptr_stride, src_idx0, dst0, tbl, len, k, nitems, tiles, out, \
-                                     r0, col0, r0m, c0m, sbad);                                                 \
-    break;
-#define EC_VCASE_U(n) EC_VCASE(n, 10) EC_VCASE(n, 8) EC_VCASE(n, 6) EC_VCASE(n, 4)
-    EC_VCASE_U(1) EC_VCASE_U(2) EC_VCASE_U(3) EC_VCASE_U(4) EC_VCASE_U(5) EC_VCASE_U(6) EC_VCASE_U(7) EC_VCASE_U(8)
-#undef EC_VCASE_U
-#undef EC_VCASE
-  }
+// A verify pass's rows, load group and 0/1 form as template arguments:
+// f(P, U, FL); false (f not called) when the pass has no row count of 1..8.
+template <class F>
+static bool with_verify_case(int P, int k, bool x, F&& f) {
+  return with_rows(P, [&](auto p) {
+    with_verify_group(k, [&](auto u) { with_xor(x, [&](auto fl) { f(p, u, fl); }); });
+  });
+}
+
+// One pass of the 16-byte verify over nitems items of d_ptrs.
+static void verify_pass_v16(const Pass& p, unsigned grid, hipStream_t s, const uint64_t* d_ptrs, int ptr_stride,
+                            int src_idx0, int dst_idx0, int len, int k, unsigned nitems, unsigned tiles,
+                            unsigned long long* out, long long col0, unsigned long long* sbad) {
+  with_verify_case(p.P, k, p.m.x, [&](auto P, auto U, auto FL) {
+    ISAL_LAUNCH((ec_verify_v16<decltype(P)::value, EncPol<decltype(U)::value, kBufNT, kBufNT, 0>, decltype(FL)::value>),
+                dim3(grid), dim3(kBlock), 0, s, d_ptrs, ptr_stride, src_idx0, dst_idx0 + p.r0, p.tbl, len, k, nitems,
+                tiles, out, p.r0, col0, p.m.r0m, p.m.c0m, sbad);
+  });
 }
 
 extern "C" int isal_hip_launch_verify(const uint64_t* d_ptrs, int ptr_stride, int src_idx0,
@@ -1733,40 +1741,21 @@ extern "C" int isal_hip_launch_verify(const uint64_t* d_ptrs, int ptr_stride, in
   *nslots = 0;
   if (len <= 0 || rows <= 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  em = enc_xor_masks(em);
-  const unsigned span = vec16 ? kTile : kBlock;
-  const unsigned tiles = static_cast<unsigned>((static_cast<long long>(len) + span - 1) / span);
+  const unsigned tiles = tiles_of(len, vec16 ? kTile : kBlock);
   const unsigned grid = tiles < EC_VERIFY_MAX_GRID ? tiles : EC_VERIFY_MAX_GRID;
-  const int U = verify_group(k);
-  for (int r0 = 0; r0 < rows; r0 += EC_MAX_ROWS_PER_PASS) {
-    const int P = rows - r0 < EC_MAX_ROWS_PER_PASS ? rows - r0 : EC_MAX_ROWS_PER_PASS;
-    const uint32_t* tbl = d_tbl + static_cast<size_t>(kTbl) * k * r0;
-    const int dst0 = dst_idx0 + r0;
-    const int g = r0 / EC_MAX_ROWS_PER_PASS;
-    const bool x = em && g < EC_MAX_PASSES && ((em->ok >> g) & 1u);
-    const unsigned long long r0m = x ? em->r0[g] : 0ull;
-    const unsigned c0m = x ? em->c0[g] : 0u;
+  return for_passes(d_tbl, k, rows, em, [&](const Pass& p) {
     unsigned long long* out = slots + *nslots;
     if (!vec16) {
-      switch (P) {
-#define EC_CASE(n)                                                                                      \
-  case n:                                                                                               \
-    ISAL_LAUNCH(ec_verify_b1<n>, dim3(grid), dim3(kBlock), 0, s, d_ptrs, ptr_stride, src_idx0, dst0, \
-                       tbl, len, k, tiles, tiles, out, r0, col0);                                       \
-    break;
-        EC_CASE(1) EC_CASE(2) EC_CASE(3) EC_CASE(4) EC_CASE(5) EC_CASE(6) EC_CASE(7) EC_CASE(8)
-#undef EC_CASE
-      }
+      with_rows(p.P, [&](auto P) {
+        ISAL_LAUNCH(ec_verify_b1<decltype(P)::value>, dim3(grid), dim3(kBlock), 0, s, d_ptrs, ptr_stride, src_idx0,
+                    dst_idx0 + p.r0, p.tbl, len, k, tiles, tiles, out, p.r0, col0);
+      });
     } else {
-      verify_pass_v16(P, U, x, grid, s, d_ptrs, ptr_stride, src_idx0, dst0, tbl, len, k, tiles, tiles, out, r0, col0,
-                      r0m, c0m, nullptr);
+      verify_pass_v16(p, grid, s, d_ptrs, ptr_stride, src_idx0, dst_idx0, len, k, tiles, tiles, out, col0, nullptr);
     }
     *nslots += static_cast<int>(grid);
-    isal_hip_count_launch();
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return static_cast<int>(e);
-  }
-  return 0;
+    return hipSuccess;
+  });
 }
 
 extern "C" int isal_hip_launch_verify_batch(const uint64_t* d_ptrs, int ptr_stride, int src_idx0, int dst_idx0,
@@ -1776,26 +1765,15 @@ extern "C" int isal_hip_launch_verify_batch(const uint64_t* d_ptrs, int ptr_stri
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipError_t e = hipMemsetAsync(bad, 0xff, static_cast<size_t>(nstripes) * 8, s);
   if (e != hipSuccess) return static_cast<int>(e);
-  em = enc_xor_masks(em);
-  const unsigned per = stripes_per_launch(len, true);
-  const unsigned tiles = static_cast<unsigned>((static_cast<long long>(len) + kTile - 1) / kTile);
-  const int U = verify_group(k);
-  for (long long s0 = 0; s0 < nstripes; s0 += per) {
-    const unsigned ns = static_cast<unsigned>(nstripes - s0 < per ? nstripes - s0 : per);
-    const uint64_t* ptrs = d_ptrs + s0 * ptr_stride;
-    for (int r0 = 0; r0 < rows; r0 += EC_MAX_ROWS_PER_PASS) {
-      const int P = rows - r0 < EC_MAX_ROWS_PER_PASS ? rows - r0 : EC_MAX_ROWS_PER_PASS;
-      const int g = r0 / EC_MAX_ROWS_PER_PASS;
-      const bool x = em && g < EC_MAX_PASSES && ((em->ok >> g) & 1u);
-      verify_pass_v16(P, U, x, ns * tiles, s, ptrs, ptr_stride, src_idx0, dst_idx0 + r0,
-                      d_tbl + static_cast<size_t>(kTbl) * k * r0, len, k, ns * tiles, tiles, nullptr, r0, 0,
-                      x ? em->r0[g] : 0ull, x ? em->c0[g] : 0u, bad + s0);
-      isal_hip_count_launch();
-      e = hipGetLastError();
-      if (e != hipSuccess) return static_cast<int>(e);
-    }
-  }
-  return 0;
+  const unsigned tiles = tiles_of(len, kTile);
+  return for_slices(d_ptrs, ptr_stride, nstripes, stripes_per_launch(len, true),
+                    [&](long long s0, unsigned ns, const uint64_t* ptrs) {
+                      return for_passes(d_tbl, k, rows, em, [&](const Pass& p) {
+                        verify_pass_v16(p, ns * tiles, s, ptrs, ptr_stride, src_idx0, dst_idx0, len, k, ns * tiles,
+                                        tiles, nullptr, 0, bad + s0);
+                        return hipSuccess;
+                      });
+                    });
 }
 
 // The scrub batch's launch: verdict (nstripes words) is filled with "clean" on
@@ -1809,37 +1787,22 @@ extern "C" int isal_hip_launch_locate_batch(const uint64_t* d_ptrs, int ptr_stri
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipError_t e = hipMemsetAsync(verdict, 0xff, static_cast<size_t>(nstripes) * 4, s);
   if (e != hipSuccess) return static_cast<int>(e);
-  em = enc_xor_masks(em);
-  const bool x = em && (em->ok & 1u);
-  const unsigned long long r0m = x ? em->r0[0] : 0ull;
-  const unsigned c0m = x ? em->c0[0] : 0u;
-  const unsigned per = stripes_per_launch(len, true);
-  const unsigned tiles = static_cast<unsigned>((static_cast<long long>(len) + kTile - 1) / kTile);
-  const int U = verify_group(k);
-  for (long long s0 = 0; s0 < nstripes; s0 += per) {
-    const unsigned ns = static_cast<unsigned>(nstripes - s0 < per ? nstripes - s0 : per);
-    const uint64_t* ptrs = d_ptrs + s0 * ptr_stride;
-    const unsigned nitems = ns * tiles;
-    switch (rows * 64 + U * 2 + (x ? 1 : 0)) {
-#define EC_LCASE(n, u)                                                                                          \
-  case n * 64 + u * 2:                                                                                          \
-    ISAL_LAUNCH((ec_locate_v16<n, EncPol<u, kBufNT, kBufNT, 0>, kEncLUT>), dim3(nitems), dim3(kBlock), 0, s,    \
-                ptrs, ptr_stride, d_tbl, len, k, nitems, tiles, 0ull, 0u, d_loc, verdict + s0);                 \
-    break;                                                                                                      \
-  case n * 64 + u * 2 + 1:                                                                                      \
-    ISAL_LAUNCH((ec_locate_v16<n, EncPol<u, kBufNT, kBufNT, 0>, kEncXor>), dim3(nitems), dim3(kBlock), 0, s,    \
-                ptrs, ptr_stride, d_tbl, len, k, nitems, tiles, r0m, c0m, d_loc, verdict + s0);                 \
-    break;
-#define EC_LCASE_U(n) EC_LCASE(n, 10) EC_LCASE(n, 8) EC_LCASE(n, 6) EC_LCASE(n, 4)
-      EC_LCASE_U(2) EC_LCASE_U(3) EC_LCASE_U(4) EC_LCASE_U(5) EC_LCASE_U(6) EC_LCASE_U(7) EC_LCASE_U(8)
-#undef EC_LCASE_U
-#undef EC_LCASE
-    }
-    isal_hip_count_launch();
-    e = hipGetLastError();
-    if (e != hipSuccess) return static_cast<int>(e);
-  }
-  return 0;
+  const unsigned tiles = tiles_of(len, kTile);
+  return for_slices(
+      d_ptrs, ptr_stride, nstripes, stripes_per_launch(len, true),
+      [&](long long s0, unsigned ns, const uint64_t* ptrs) {
+        const unsigned nitems = ns * tiles;
+        return for_passes(d_tbl, k, rows, em, [&](const Pass& p) {  // one pass: rows <= 8
+          with_verify_case(p.P, k, p.m.x, [&](auto P, auto U, auto FL) {
+            if constexpr (decltype(P)::value >= 2)  // a single row names no shard
+              ISAL_LAUNCH((ec_locate_v16<decltype(P)::value, EncPol<decltype(U)::value, kBufNT, kBufNT, 0>,
+                                         decltype(FL)::value>),
+                          dim3(nitems), dim3(kBlock), 0, s, ptrs, ptr_stride, p.tbl, len, k, nitems, tiles, p.m.r0m,
+                          p.m.c0m, d_loc, verdict + s0);
+          });
+          return hipSuccess;
+        });
+      });
 }
 
 // The ragged batch's encode: one ec_encode_rag launch per pass of rows, each
@@ -1851,25 +1814,19 @@ extern "C" int isal_hip_launch_encode_ragged(const uint64_t* d_ptrs, int ptr_str
   if (rows <= 0 || nitems == 0) return 0;  // every length 0: no tile of either size
   if (k < 1 || nitems > kMaxItems || nitems_small > kMaxItems) return static_cast<int>(hipErrorInvalidValue);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  for (int r0 = 0; r0 < rows; r0 += EC_MAX_ROWS_PER_PASS) {
-    const int P = rows - r0 < EC_MAX_ROWS_PER_PASS ? rows - r0 : EC_MAX_ROWS_PER_PASS;
-    const bool small = P <= ISAL_HIP_RAGGED_SMALL_ROWS;
+  return for_passes(d_tbl, k, rows, nullptr, [&](const Pass& p) {
+    const bool small = p.P <= ISAL_HIP_RAGGED_SMALL_ROWS;
     const uint2* items = reinterpret_cast<const uint2*>(small ? d_items_small : d_items);
     const unsigned n = small ? nitems_small : nitems;
-    const uint32_t* tbl = d_tbl + static_cast<size_t>(kTbl) * k * r0;
-    if (!items || n == 0) return static_cast<int>(hipErrorInvalidValue);
-    hipError_t e = hipSuccess;
-    switch (P) {
-#define EC_CASE(p)                                                                        \
-  case p:                                                                                 \
-    e = encode_rag_pass<p>(s, d_ptrs, ptr_stride, items, d_lens, tbl, k + r0, k, n); \
-    break;
-      EC_CASE(1) EC_CASE(2) EC_CASE(3) EC_CASE(4) EC_CASE(5) EC_CASE(6) EC_CASE(7) EC_CASE(8)
-#undef EC_CASE
-    }
-    if (e != hipSuccess) return static_cast<int>(e);
-  }
-  return 0;
+    if (!items || n == 0) return hipErrorInvalidValue;
+    with_rows(p.P, [&](auto P) {
+      with_enc_group(k, p.P, [&](auto u) {
+        launch_encode_rag<decltype(P)::value, decltype(u)::value>(s, d_ptrs, ptr_stride, items, d_lens, p.tbl,
+                                                                  k + p.r0, k, n);
+      });
+    });
+    return hipSuccess;
+  });
 }
 
 // The ragged batch's check: bad (nstripes words) is filled with ~0 on the
@@ -1884,26 +1841,15 @@ extern "C" int isal_hip_launch_verify_ragged(const uint64_t* d_ptrs, int ptr_str
   hipError_t e = hipMemsetAsync(bad, 0xff, static_cast<size_t>(nstripes) * 8, s);
   if (e != hipSuccess) return static_cast<int>(e);
   const uint2* items = reinterpret_cast<const uint2*>(d_items);
-  const int U = verify_group(k);
-  for (int r0 = 0; r0 < rows; r0 += EC_MAX_ROWS_PER_PASS) {
-    const int P = rows - r0 < EC_MAX_ROWS_PER_PASS ? rows - r0 : EC_MAX_ROWS_PER_PASS;
-    const uint32_t* tbl = d_tbl + static_cast<size_t>(kTbl) * k * r0;
-    switch (P * 16 + U) {
-#define EC_RCASE(p, u)                                                                                          \
-  case p * 16 + u:                                                                                              \
-    ISAL_LAUNCH((ec_verify_rag<p, EncPol<u, kBufNT, kBufNT, 0>>), dim3(nitems), dim3(kBlock), 0, s, d_ptrs,     \
-                ptr_stride, items, d_lens, tbl, k + r0, r0, k, nitems, bad);                                    \
-    break;
-#define EC_RCASE_U(p) EC_RCASE(p, 10) EC_RCASE(p, 8) EC_RCASE(p, 6) EC_RCASE(p, 4)
-      EC_RCASE_U(1) EC_RCASE_U(2) EC_RCASE_U(3) EC_RCASE_U(4) EC_RCASE_U(5) EC_RCASE_U(6) EC_RCASE_U(7) EC_RCASE_U(8)
-#undef EC_RCASE_U
-#undef EC_RCASE
-    }
-    isal_hip_count_launch();
-    e = hipGetLastError();
-    if (e != hipSuccess) return static_cast<int>(e);
-  }
-  return 0;
+  return for_passes(d_tbl, k, rows, nullptr, [&](const Pass& p) {
+    with_rows(p.P, [&](auto P) {
+      with_verify_group(k, [&](auto U) {
+        ISAL_LAUNCH((ec_verify_rag<decltype(P)::value, EncPol<decltype(U)::value, kBufNT, kBufNT, 0>>), dim3(nitems),
+                    dim3(kBlock), 0, s, d_ptrs, ptr_stride, items, d_lens, p.tbl, k + p.r0, p.r0, k, nitems, bad);
+      });
+    });
+    return hipSuccess;
+  });
 }
 
 extern "C" int isal_hip_launch_verify_karg(const isal_hip_karg* a, const isal_hip_kdone* d, int len, int k,
@@ -1913,27 +1859,14 @@ extern "C" int isal_hip_launch_verify_karg(const isal_hip_karg* a, const isal_hi
       static_cast<size_t>(kTbl) * k * rows > ISAL_HIP_KARG_TBL)
     return static_cast<int>(hipErrorInvalidValue);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const unsigned tiles = static_cast<unsigned>((static_cast<long long>(len) + kTile - 1) / kTile);
-  em = enc_xor_masks(em);
-  const bool x = em && (em->ok & 1u);
-  const unsigned long long r0m = x ? em->r0[0] : 0ull;
-  const unsigned c0m = x ? em->c0[0] : 0u;
-  switch (rows * 64 + verify_group(k) * 2 + (x ? 1 : 0)) {
-#define EC_VKARG(n, u)                                                                                             \
-  case n * 64 + u * 2:                                                                                             \
-    ISAL_LAUNCH((ec_verify_karg<n, EncPol<u, kBufNT, kBufNT, 0>, kEncLUT>), dim3(tiles), dim3(kBlock), 0, s, \
-                       *a, *d, len, k, tiles, 0ull, 0u);                                                           \
-    break;                                                                                                         \
-  case n * 64 + u * 2 + 1:                                                                                         \
-    ISAL_LAUNCH((ec_verify_karg<n, EncPol<u, kBufNT, kBufNT, 0>, kEncXor>), dim3(tiles), dim3(kBlock), 0, s, \
-                       *a, *d, len, k, tiles, r0m, c0m);                                                           \
-    break;
-#define EC_VKARG_U(n) EC_VKARG(n, 10) EC_VKARG(n, 8) EC_VKARG(n, 6) EC_VKARG(n, 4)
-    EC_VKARG_U(1) EC_VKARG_U(2) EC_VKARG_U(3) EC_VKARG_U(4) EC_VKARG_U(5) EC_VKARG_U(6) EC_VKARG_U(7) EC_VKARG_U(8)
-#undef EC_VKARG_U
-#undef EC_VKARG
-    default: return static_cast<int>(hipErrorInvalidValue);
-  }
+  const unsigned tiles = tiles_of(len, kTile);
+  const PassMask m = pass_mask(em, 0);
+  if (!with_verify_case(rows, k, m.x, [&](auto P, auto U, auto FL) {
+        ISAL_LAUNCH(
+            (ec_verify_karg<decltype(P)::value, EncPol<decltype(U)::value, kBufNT, kBufNT, 0>, decltype(FL)::value>),
+            dim3(tiles), dim3(kBlock), 0, s, *a, *d, len, k, tiles, m.r0m, m.c0m);
+      }))
+    return static_cast<int>(hipErrorInvalidValue);
   isal_hip_count_launch();
   return static_cast<int>(hipGetLastError());
 }
@@ -1943,26 +1876,15 @@ extern "C" int isal_hip_launch_update(const uint64_t* d_ptrs, int ptr_stride, in
                                       int vec_i, long long nstripes, int vec16, void* stream) {
   if (len <= 0 || rows <= 0 || nstripes <= 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const unsigned per = stripes_per_launch(len, vec16 != 0, kUpdTile);
-  for (long long s0 = 0; s0 < nstripes; s0 += per) {
-    const unsigned ns = static_cast<unsigned>(nstripes - s0 < per ? nstripes - s0 : per);
-    const uint64_t* ptrs = d_ptrs + s0 * ptr_stride;
-    for (int r0 = 0; r0 < rows; r0 += EC_MAX_ROWS_PER_PASS) {
-      const int P = rows - r0 < EC_MAX_ROWS_PER_PASS ? rows - r0 : EC_MAX_ROWS_PER_PASS;
-      const uint32_t* tbl =
-          d_tbl + static_cast<size_t>(kTbl) * k * r0 + static_cast<size_t>(vec_i) * P * kTbl;
-      const int dst0 = dst_idx0 + r0;
-      hipError_t e = hipSuccess;
-      switch (P) {
-#define EC_CASE(n)                                                                          \
-  case n:                                                                                   \
-    e = update_pass<n>(ptrs, ptr_stride, src_idx, dst0, tbl, len, ns, vec16 != 0, s); \
-    break;
-        EC_CASE(1) EC_CASE(2) EC_CASE(3) EC_CASE(4) EC_CASE(5) EC_CASE(6) EC_CASE(7) EC_CASE(8)
-#undef EC_CASE
-      }
-      if (e != hipSuccess) return static_cast<int>(e);
-    }
-  }
-  return 0;
+  return for_slices(d_ptrs, ptr_stride, nstripes, stripes_per_launch(len, vec16 != 0, kUpdTile),
+                    [&](long long, unsigned ns, const uint64_t* ptrs) {
+                      return for_passes(d_tbl, k, rows, nullptr, [&](const Pass& p) {
+                        with_rows(p.P, [&](auto P) {
+                          update_pass<decltype(P)::value>(ptrs, ptr_stride, src_idx, dst_idx0 + p.r0,
+                                                          p.tbl + static_cast<size_t>(vec_i) * p.P * kTbl, len, ns,
+                                                          vec16 != 0, s);
+                        });
+                        return hipSuccess;
+                      });
+                    });
 }

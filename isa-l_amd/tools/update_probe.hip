@@ -18,6 +18,7 @@ extern "C" void gf_gen_rs_matrix(unsigned char* a, int m, int k);
 extern "C" void ec_init_tables(int k, int rows, unsigned char* a, unsigned char* gftbls);
 extern "C" void isal_hip_count_launch(void) {}
 extern "C" long long isal_hip_knob(int) { return -1; }
+extern "C" void isal_hip_kreg_add(const void*, const char*) {}
 
 #define CK(x)                                                                          \
   do {                                                                                 \
