@@ -172,7 +172,8 @@ int isal_hip_decode_matrix(int k, int m, const unsigned char *a, int nerrs,
  * nerrs = 3 layout; far past the few MiB of L2 that let neighbouring
  * workgroups share a pattern's tables) is refused with ISAL_HIP_ENOMEM.
  * Out of scope: erasure counts that differ within one object (one object per
- * count), unaligned or host-pageable shards, and any CPU route.
+ * count; isal_hip_repair_create_ragged below lifts this and the single len),
+ * unaligned or host-pageable shards, and any CPU route.
  */
 #define ISAL_HIP_REPAIR_MAX_TABLE_BYTES (64u << 20)
 typedef struct isal_hip_repair isal_hip_repair;
@@ -183,6 +184,66 @@ int isal_hip_repair_run(isal_hip_repair *r, void *stream);
 /* distinct erasure patterns found by create */
 int isal_hip_repair_npatterns(const isal_hip_repair *r);
 int isal_hip_repair_destroy(isal_hip_repair *r);
+
+/*
+ * Ragged repair: the same object for a real rebuild window, where every
+ * stripe has its OWN shard length (objects of every size, short last stripes)
+ * and its OWN erasure count (after a second device loss stripes have lost 0,
+ * 1 or 2 shards). isal_hip_repair_run, _npatterns and _destroy serve both
+ * kinds of object.
+ *   lens:     nstripes byte lengths; lens[s] is the length of every shard of
+ *             stripe s. Any value >= 0 is valid.
+ *   max_errs: the stride of errs, 1 <= max_errs <= m - k.
+ *   nerrs:    nstripes counts, nerrs[s] in [0, max_errs].
+ *   errs:     errs[s*max_errs + i] for i < nerrs[s] are stripe s's erased
+ *             indices (in range, distinct, any order); the rest of the row is
+ *             ignored.
+ *   shards:   as for isal_hip_repair_create.
+ * A stripe with lens[s] == 0 or nerrs[s] == 0 is neither read nor written.
+ * Every other stripe is rebuilt byte-identically to ec_encode_data(lens[s], k,
+ * nerrs[s], the tables of isal_hip_decode_matrix(...), survivors, erased);
+ * nothing outside [0, lens[s]) of the erased shards is written.
+ * Refused, all before the first HIP call, so a host without a GPU answers the
+ * same; *bad_stripe (optional) as for the other batches:
+ *   ISAL_HIP_EINVAL     NULL arguments, nstripes <= 0, k < 1, m <= k, m > 256
+ *                       or max_errs out of range (*bad_stripe = -1);
+ *   ISAL_HIP_EINVAL     nerrs[s] > max_errs, a negative lens[s], a bad or
+ *                       duplicate index, a NULL shard pointer or one not
+ *                       16-byte aligned (stripes of zero length or zero count
+ *                       included); *bad_stripe names the first such stripe;
+ *   ISAL_HIP_ESINGULAR  *bad_stripe names the first undecodable stripe;
+ *   ISAL_HIP_ENOMEM     the coefficient tables of all distinct patterns of
+ *                       all counts together exceed
+ *                       ISAL_HIP_REPAIR_MAX_TABLE_BYTES;
+ *   ISAL_HIP_EINVAL     one count class (below) has more than 2^30 work items
+ *                       at the smallest tile its passes use, the limit of one
+ *                       launch (*bad_stripe = -1).
+ * isal_hip_repair_npatterns counts distinct erasure sets; sets of different
+ * counts are different patterns, and stripes that lost nothing contribute
+ * none. Memory kinds and device ownership as for isal_hip_batch_create; a
+ * shard must be reachable over its own stripe's length.
+ * isal_hip_repair_run only enqueues. The stripes are grouped into count
+ * classes: class c holds the stripes with nerrs[s] == c and lens[s] > 0. Each
+ * class present is launched once per pass of isal_hip_max_rows_per_pass()
+ * rows, in ascending c: a run takes the sum over those classes of
+ * ceil(c / max_rows_per_pass) launches (counted by isal_hip_kernel_launches),
+ * none when no class is present, and is idempotent. Work items are 4 KiB
+ * tiles of one row; a pass of 1-2 rows runs on 2 KiB tiles, as in the ragged
+ * batch.
+ * Device memory: the coefficient tables (20*k*c bytes per distinct pattern of
+ * count c) and one more allocation that holds, per class, the pointer table
+ * (8*(k + c) bytes per row), 4 bytes of pattern word and 4 bytes of length
+ * per row, and 8 bytes per tile of one shard for each tile size the class's
+ * passes use (0.2 % of one shard's bytes at 4 KiB; c % 8 == 1 or 2 adds or
+ * takes instead a table per 2 KiB tile).
+ * Out of scope: unaligned or host-pageable shards, any CPU route, set_tables,
+ * and the LDS-staged and LDS product-table wide kernels (every pass takes the
+ * plain lookup kernel).
+ */
+int isal_hip_repair_create_ragged(isal_hip_repair **out, int k, int m, const unsigned char *a,
+                                  int nstripes, const int *lens, int max_errs,
+                                  const unsigned char *nerrs, const unsigned char *errs,
+                                  unsigned char *const *shards, int *bad_stripe);
 
 /* ---- overwrite batch: partial-stripe writes folded into parity ----------- */
 

@@ -1417,6 +1417,58 @@ void launch_encode_rag(hipStream_t s, const uint64_t* ptrs, int ptr_stride, cons
 }
 
 // ---------------------------------------------------------------------------
+// Ragged repair (isal_hip_repair.c isal_hip_repair_create_ragged, DESIGN §3
+// "Ragged repair"): ec_repair_v16's pattern lookup on ec_encode_rag's items.
+// The item table gives {row, tile} of one count class's pointer table (k
+// survivors then P destinations per row), lens[row] bounds every load and
+// store, and pat[row] is the dword offset of the row's pattern in the table
+// array (tbl0 already points at the pass): patterns of different counts have
+// tables of different sizes, so the word is an offset, not an index. All of
+// them are scalar loads that readfirstlane pins to SGPRs. Always the plain
+// lookup form (kEncLUT), as both parents.
+// ---------------------------------------------------------------------------
+template <int P, class Pol, int B>
+__global__ __launch_bounds__(B, (enc_waves<P, Pol::U, kEncLUT>())) void ec_repair_rag(
+    const uint64_t* __restrict__ ptrs, int ptr_stride, const uint2* __restrict__ items,
+    const int* __restrict__ lens, const uint32_t* __restrict__ pat, const uint32_t* __restrict__ tbl0, int dst0,
+    int k, unsigned nitems) {
+  if (blockIdx.x >= nitems) return;
+  const RagItem it = rag_item(items, lens, nitems);
+  const uint64_t* __restrict__ sp = ptrs + static_cast<size_t>(it.stripe) * ptr_stride;
+  const unsigned p = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(pat[it.stripe])));
+  const uint32_t* __restrict__ tbl = tbl0 + p;
+  const long long off = static_cast<long long>(it.tile) * (B * kVec) + threadIdx.x * kVec;
+  if constexpr ((P == 7 && Pol::U == 4) || (P == 4 && Pol::U == 8)) {
+    // The two instantiations ec_encode_rag writes out, for the same reason:
+    // through the call ec_repair_rag<7, EncPol<4, ..>, 256> takes 90 VGPRs
+    // instead of 78 and <4, EncPol<8, ..>, 256> 74 instead of 72, each a wave
+    // per SIMD less (profiles/repair_ragged_resources.tsv).
+    const int len = it.len;
+    if (off + kVec <= len) {
+      uint32_t acc[P][4];
+      accum16<P, Pol, kEncLUT>(acc, sp, tbl, k, off, len);
+#pragma unroll
+      for (int l = 0; l < P; ++l)
+        store16<Pol::ST>(sp[dst0 + l], off, make_uint4(acc[l][0], acc[l][1], acc[l][2], acc[l][3]), len);
+    } else if (off < len) {
+      dot_bytes<P>(sp, 0, dst0, tbl, k, off, static_cast<int>(len - off));
+    }
+  } else {
+    encode_tile<P, Pol, kEncLUT>(sp, 0, dst0, tbl, k, off, it.len, 0ull, 0u, nullptr);
+  }
+}
+
+// One pass of P rows over nitems items, launched like ec_encode_rag.
+template <int P, int U>
+void launch_repair_rag(hipStream_t s, const uint64_t* ptrs, int ptr_stride, const uint2* items, const int* lens,
+                       const uint32_t* pat, const uint32_t* tbl0, int dst0, int k, unsigned nitems) {
+  constexpr int B = enc_block<P>();
+  if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2) fprintf(stderr, "isal_hip: kernel ec_repair_rag<%d, %d, %d>\n", P, U, B);
+  ISAL_LAUNCH((ec_repair_rag<P, EncPol<U, kBufNT, kBufNT, 2>, B>), dim3(grid_for(nitems)), dim3(B),
+              enc_lds_alloc(0, P), s, ptrs, ptr_stride, items, lens, pat, tbl0, dst0, k, nitems);
+}
+
+// ---------------------------------------------------------------------------
 // Overwrite: the partial-stripe write of an encoded stripe
 // (isal_hip_overwrite.c, DESIGN §3 "Overwrite batch"):
 //   coding[l] ^= c[l][j] * (old_j ^ new_j)   for the nw rewritten shards j
@@ -1822,6 +1874,30 @@ extern "C" int isal_hip_launch_encode_ragged(const uint64_t* d_ptrs, int ptr_str
     with_rows(p.P, [&](auto P) {
       with_enc_group(k, p.P, [&](auto u) {
         launch_encode_rag<decltype(P)::value, decltype(u)::value>(s, d_ptrs, ptr_stride, items, d_lens, p.tbl,
+                                                                  k + p.r0, k, n);
+      });
+    });
+    return hipSuccess;
+  });
+}
+
+// One count class of a ragged repair: one ec_repair_rag launch per pass of
+// rows, each over the class's item table of its tile size.
+extern "C" int isal_hip_launch_repair_ragged(const uint64_t* d_ptrs, int ptr_stride, const uint32_t* d_pat,
+                                             const uint32_t* d_tbl, const int* d_lens, const unsigned* d_items,
+                                             unsigned nitems, const unsigned* d_items_small, unsigned nitems_small,
+                                             int k, int rows, void* stream) {
+  if (rows <= 0 || (nitems == 0 && nitems_small == 0)) return 0;
+  if (k < 1 || nitems > kMaxItems || nitems_small > kMaxItems) return static_cast<int>(hipErrorInvalidValue);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return for_passes(d_tbl, k, rows, nullptr, [&](const Pass& p) {
+    const bool small = p.P <= ISAL_HIP_RAGGED_SMALL_ROWS;
+    const uint2* items = reinterpret_cast<const uint2*>(small ? d_items_small : d_items);
+    const unsigned n = small ? nitems_small : nitems;
+    if (!items || n == 0) return hipErrorInvalidValue;
+    with_rows(p.P, [&](auto P) {
+      with_enc_group(k, p.P, [&](auto u) {
+        launch_repair_rag<decltype(P)::value, decltype(u)::value>(s, d_ptrs, ptr_stride, items, d_lens, d_pat, p.tbl,
                                                                   k + p.r0, k, n);
       });
     });

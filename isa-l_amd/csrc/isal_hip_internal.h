@@ -292,6 +292,19 @@ int isal_hip_launch_verify_ragged(const uint64_t *d_ptrs, int ptr_stride, const 
                                   const int *d_lens, const unsigned *d_items, unsigned nitems, int k,
                                   int rows, long long nstripes, unsigned long long *bad, void *stream);
 
+/* Ragged repair (ec_kernels.hip ec_repair_rag): one count class of
+ * isal_hip_repair_create_ragged, the rows that lost `rows` shards. Pointer rows
+ * are k survivors then rows destinations (stride ptr_stride, every pointer
+ * 16-byte aligned); row r has length d_lens[r] and takes the coefficient
+ * tables at d_tbl + d_pat[r] dwords, laid out like one encode's tables. Items
+ * are {row, tile} pairs as for isal_hip_launch_encode_ragged, and so are the
+ * tile sizes: either table may be NULL when rows has no pass of its size. One
+ * launch per pass; nothing is enqueued when both item counts are 0. */
+int isal_hip_launch_repair_ragged(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_pat,
+                                  const uint32_t *d_tbl, const int *d_lens, const unsigned *d_items,
+                                  unsigned nitems, const unsigned *d_items_small, unsigned nitems_small,
+                                  int k, int rows, void *stream);
+
 /* Kernel registry (isal_hip_selftest_kernels): every kernel a launcher can
  * launch registers its host handle and a name when the library loads
  * (ec_device.h ISAL_LAUNCH). */

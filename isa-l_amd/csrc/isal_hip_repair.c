@@ -16,6 +16,17 @@
  *      coefficient lines (ec_kernels.hip ec_repair_v16).
  * A repair batch belongs to the device that was current when it was created
  * (ON_BATCH_DEVICE).
+ *
+ * isal_hip_repair_create_ragged builds the same object for stripes that each
+ * have their own length and their own erasure count. A pattern is then the
+ * pair (count, erasure set), and the stripes are grouped into count classes:
+ * class c holds the stripes of non-zero length that lost c shards, and gets
+ * what the uniform create builds for the whole object (rows sorted by
+ * pattern, k survivors then c destinations, a pattern word per row) plus a
+ * length per row and the ragged batch's item tables, one per tile size its
+ * passes use. Patterns of different counts have tables of different sizes, so
+ * a row's pattern word is the dword offset of its tables in the one table
+ * array. Everything but the tables travels in one device allocation.
  */
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -28,12 +39,32 @@
 
 #define MAX_SHARDS 256 /* shard indices are bytes */
 
+enum { BIG, SMALL, NTILES }; /* ISAL_HIP_RAGGED_TILE, ISAL_HIP_RAGGED_TILE_SMALL */
+
+/* one count class of a ragged repair; the device pointers lie in d_blob */
+typedef struct {
+        int nerrs;
+        unsigned nrows, nitems[NTILES];
+        uint64_t *d_ptrs;
+        uint32_t *d_pat;
+        int *d_lens;
+        unsigned *d_items[NTILES];
+} rclass;
+
 struct isal_hip_repair {
         int len, k, nerrs, nstripes, npat, device;
         unsigned tbl_stride; /* dwords per pattern */
         uint64_t *d_ptrs;
         uint32_t *d_pat, *d_tbl;
+        /* isal_hip_repair_create_ragged: classes in ascending count */
+        int ragged, nclass;
+        rclass *cls;
+        unsigned char *d_blob;
 };
+
+/* tests/sanitize/repair_host.c links this file without the ragged pieces */
+#pragma weak isal_hip_ragged_items
+#pragma weak isal_hip_launch_repair_ragged
 
 /* errs in range and distinct; mark[] (MAX_SHARDS bytes) receives the set */
 static int
@@ -90,13 +121,16 @@ isal_hip_decode_matrix(int k, int m, const unsigned char *a, int nerrs, const un
 
 /* ---- the distinct patterns of one create ---------------------------------- */
 
+/* A pattern is (count, ascending erasure set): its key is kw = 1 + the largest
+ * count bytes, the count, the set, then zeros. */
 typedef struct {
-        int k, m, nerrs, npat, cap;
-        unsigned tbl_stride;
+        int k, m, kw, npat, cap;
+        size_t tbl_dwords, tbl_cap; /* used, allocated */
         const unsigned char *a;
-        unsigned char *keys;  /* [npat][nerrs] ascending erasure sets */
+        unsigned char *keys;  /* [npat][kw] */
         unsigned char *surv;  /* [npat][k] */
-        uint32_t *tbl;        /* [npat][tbl_stride] */
+        uint32_t *off;        /* [npat] dword offset of the pattern's tables in tbl */
+        uint32_t *tbl;        /* every pattern's device table image, in order of first use */
         int32_t *slot;        /* open-addressing table of pattern indices, -1 empty */
         size_t nslot;         /* a power of two */
         unsigned char *c, *g; /* scratch: recovery rows, ec_init_tables output */
@@ -107,62 +141,106 @@ patset_free(patset *ps)
 {
         free(ps->keys);
         free(ps->surv);
+        free(ps->off);
         free(ps->tbl);
         free(ps->slot);
         free(ps->c);
         free(ps->g);
 }
 
+/* an empty set for patterns of up to max_errs erasures among nstripes stripes */
 static int
-patset_grow(patset *ps)
+patset_init(patset *ps, int k, int m, const unsigned char *a, int max_errs, int nstripes)
 {
-        const int cap = ps->cap ? 2 * ps->cap : 16;
-        unsigned char *keys = (unsigned char *) realloc(ps->keys, (size_t) cap * ps->nerrs);
-        unsigned char *surv;
-        uint32_t *tbl;
-        if (!keys)
+        memset(ps, 0, sizeof(*ps));
+        ps->k = k;
+        ps->m = m;
+        ps->kw = 1 + max_errs;
+        ps->a = a;
+        for (ps->nslot = 64; ps->nslot < 2 * (size_t) nstripes; ps->nslot *= 2)
+                ;
+        ps->slot = (int32_t *) malloc(ps->nslot * sizeof(int32_t));
+        ps->c = (unsigned char *) malloc((size_t) max_errs * k);
+        ps->g = (unsigned char *) malloc(32 * (size_t) max_errs * k);
+        if (!ps->slot || !ps->c || !ps->g)
                 return ISAL_HIP_ENOMEM;
-        ps->keys = keys;
-        surv = (unsigned char *) realloc(ps->surv, (size_t) cap * ps->k);
-        if (!surv)
-                return ISAL_HIP_ENOMEM;
-        ps->surv = surv;
-        tbl = (uint32_t *) realloc(ps->tbl, (size_t) cap * ps->tbl_stride * 4);
-        if (!tbl)
-                return ISAL_HIP_ENOMEM;
-        ps->tbl = tbl;
-        ps->cap = cap;
+        memset(ps->slot, 0xff, ps->nslot * sizeof(int32_t));
         return ISAL_HIP_OK;
 }
 
-/* Index of the ascending erasure set key, adding it (recovery rows, device
- * table image) when new; a negative ISAL_HIP_E* code otherwise. */
+/* room for one more pattern whose tables take `dwords` */
 static int
-patset_find(patset *ps, const unsigned char *key)
+patset_grow(patset *ps, size_t dwords)
 {
+        if (ps->npat == ps->cap) {
+                const int cap = ps->cap ? 2 * ps->cap : 16;
+                unsigned char *keys = (unsigned char *) realloc(ps->keys, (size_t) cap * ps->kw);
+                unsigned char *surv;
+                uint32_t *off;
+                if (!keys)
+                        return ISAL_HIP_ENOMEM;
+                ps->keys = keys;
+                surv = (unsigned char *) realloc(ps->surv, (size_t) cap * ps->k);
+                if (!surv)
+                        return ISAL_HIP_ENOMEM;
+                ps->surv = surv;
+                off = (uint32_t *) realloc(ps->off, (size_t) cap * 4);
+                if (!off)
+                        return ISAL_HIP_ENOMEM;
+                ps->off = off;
+                ps->cap = cap;
+        }
+        if (ps->tbl_dwords + dwords > ps->tbl_cap) {
+                size_t cap = ps->tbl_cap ? 2 * ps->tbl_cap : 16 * dwords;
+                uint32_t *tbl;
+                while (cap < ps->tbl_dwords + dwords)
+                        cap *= 2;
+                tbl = (uint32_t *) realloc(ps->tbl, cap * 4);
+                if (!tbl)
+                        return ISAL_HIP_ENOMEM;
+                ps->tbl = tbl;
+                ps->tbl_cap = cap;
+        }
+        return ISAL_HIP_OK;
+}
+
+/* Index of the pattern of the nerrs marked shards, adding it (recovery rows,
+ * device table image) when new; a negative ISAL_HIP_E* code otherwise. */
+static int
+patset_find(patset *ps, int nerrs, const unsigned char *mark)
+{
+        unsigned char key[1 + MAX_SHARDS];
+        const size_t dwords = isal_hip_tables_dwords(ps->k, nerrs);
         uint32_t h = 2166136261u;
         size_t at;
-        int i, r;
-        for (i = 0; i < ps->nerrs; i++)
+        int i, n = 1, r;
+        memset(key, 0, (size_t) ps->kw);
+        key[0] = (unsigned char) nerrs;
+        for (i = 0; i < ps->m; i++)
+                if (mark[i])
+                        key[n++] = (unsigned char) i;
+        for (i = 0; i < ps->kw; i++)
                 h = (h ^ key[i]) * 16777619u;
         for (at = h & (ps->nslot - 1);; at = (at + 1) & (ps->nslot - 1)) {
                 const int32_t p = ps->slot[at];
                 if (p < 0)
                         break;
-                if (!memcmp(ps->keys + (size_t) p * ps->nerrs, key, (size_t) ps->nerrs))
+                if (!memcmp(ps->keys + (size_t) p * ps->kw, key, (size_t) ps->kw))
                         return p;
         }
-        if ((size_t) (ps->npat + 1) * ps->tbl_stride * 4 > ISAL_HIP_REPAIR_MAX_TABLE_BYTES)
+        if ((ps->tbl_dwords + dwords) * 4 > ISAL_HIP_REPAIR_MAX_TABLE_BYTES)
                 return ISAL_HIP_ENOMEM;
-        if (ps->npat == ps->cap && (r = patset_grow(ps)) != ISAL_HIP_OK)
+        if ((r = patset_grow(ps, dwords)) != ISAL_HIP_OK)
                 return r;
-        r = isal_hip_decode_matrix(ps->k, ps->m, ps->a, ps->nerrs, key, ps->c,
+        r = isal_hip_decode_matrix(ps->k, ps->m, ps->a, nerrs, key + 1, ps->c,
                                    ps->surv + (size_t) ps->npat * ps->k);
         if (r != ISAL_HIP_OK)
                 return r;
-        ec_init_tables(ps->k, ps->nerrs, ps->c, ps->g);
-        isal_hip_build_tables(ps->k, ps->nerrs, ps->g, ps->tbl + (size_t) ps->npat * ps->tbl_stride);
-        memcpy(ps->keys + (size_t) ps->npat * ps->nerrs, key, (size_t) ps->nerrs);
+        ec_init_tables(ps->k, nerrs, ps->c, ps->g);
+        isal_hip_build_tables(ps->k, nerrs, ps->g, ps->tbl + ps->tbl_dwords);
+        memcpy(ps->keys + (size_t) ps->npat * ps->kw, key, (size_t) ps->kw);
+        ps->off[ps->npat] = (uint32_t) ps->tbl_dwords;
+        ps->tbl_dwords += dwords;
         ps->slot[at] = ps->npat;
         return ps->npat++;
 }
@@ -196,7 +274,7 @@ isal_hip_repair_create(isal_hip_repair **out, int len, int k, int m, const unsig
 {
         isal_hip_repair *r = NULL;
         patset ps;
-        unsigned char mark[MAX_SHARDS], key[MAX_SHARDS];
+        unsigned char mark[MAX_SHARDS];
         uint32_t *s_pat = NULL, *h_pat = NULL, *first = NULL;
         uint64_t *h_ptrs = NULL;
         long long s;
@@ -213,23 +291,12 @@ isal_hip_repair_create(isal_hip_repair **out, int len, int k, int m, const unsig
                 return ISAL_HIP_EINVAL;
         stride = (size_t) k + (size_t) nerrs;
 
-        memset(&ps, 0, sizeof(ps));
-        ps.k = k;
-        ps.m = m;
-        ps.nerrs = nerrs;
-        ps.a = a;
-        ps.tbl_stride = (unsigned) isal_hip_tables_dwords(k, nerrs);
-        for (ps.nslot = 64; ps.nslot < 2 * (size_t) nstripes; ps.nslot *= 2)
-                ;
-        ps.slot = (int32_t *) malloc(ps.nslot * sizeof(int32_t));
-        ps.c = (unsigned char *) malloc((size_t) nerrs * k);
-        ps.g = (unsigned char *) malloc(32 * (size_t) nerrs * k);
+        ret = patset_init(&ps, k, m, a, nerrs, nstripes);
         s_pat = (uint32_t *) malloc((size_t) nstripes * 4);
-        if (!ps.slot || !ps.c || !ps.g || !s_pat) {
+        if (ret == ISAL_HIP_OK && !s_pat)
                 ret = ISAL_HIP_ENOMEM;
+        if (ret != ISAL_HIP_OK)
                 goto done;
-        }
-        memset(ps.slot, 0xff, ps.nslot * sizeof(int32_t));
 
         /* 1-2: validate every stripe, find its pattern, build new patterns' tables */
         for (s = 0; s < nstripes && ret == ISAL_HIP_OK; s++) {
@@ -239,10 +306,7 @@ isal_hip_repair_create(isal_hip_repair **out, int len, int k, int m, const unsig
                         if (!sh[i] || ((uintptr_t) sh[i] & 15))
                                 ret = ISAL_HIP_EINVAL;
                 if (ret == ISAL_HIP_OK) {
-                        for (i = 0, n = 0; i < m; i++)
-                                if (mark[i])
-                                        key[n++] = (unsigned char) i;
-                        if ((n = patset_find(&ps, key)) < 0)
+                        if ((n = patset_find(&ps, nerrs, mark)) < 0)
                                 ret = n;
                         else
                                 s_pat[s] = (uint32_t) n;
@@ -274,7 +338,7 @@ isal_hip_repair_create(isal_hip_repair **out, int len, int k, int m, const unsig
                 for (i = 0; i < k; i++)
                         hp[i] = (uint64_t) (uintptr_t) sh[ps.surv[(size_t) p * k + i]];
                 for (i = 0; i < nerrs; i++)
-                        hp[k + i] = (uint64_t) (uintptr_t) sh[ps.keys[(size_t) p * nerrs + i]];
+                        hp[k + i] = (uint64_t) (uintptr_t) sh[ps.keys[(size_t) p * ps.kw + 1 + i]];
                 h_pat[row] = p;
         }
         r->len = len;
@@ -282,7 +346,8 @@ isal_hip_repair_create(isal_hip_repair **out, int len, int k, int m, const unsig
         r->nerrs = nerrs;
         r->nstripes = nstripes;
         r->npat = ps.npat;
-        r->tbl_stride = ps.tbl_stride;
+        /* one count: pattern p's tables lie at p * tbl_stride */
+        r->tbl_stride = (unsigned) isal_hip_tables_dwords(k, nerrs);
         ret = repair_upload(r, h_ptrs, h_pat, ps.tbl);
 done:
         patset_free(&ps);
@@ -298,9 +363,263 @@ done:
         return ISAL_HIP_OK;
 }
 
+/* ---- the ragged create ---------------------------------------------------- */
+
+/* whether some pass of a class of nerrs rows runs tiles of size t */
+static int
+class_uses(int nerrs, int t)
+{
+        const int last = nerrs % EC_MAX_ROWS_PER_PASS;
+        const int small = last >= 1 && last <= ISAL_HIP_RAGGED_SMALL_ROWS;
+        return t == SMALL ? small : nerrs >= EC_MAX_ROWS_PER_PASS || (last && !small);
+}
+
+/* the pieces of one class in the blob, as byte offsets */
+enum { O_PTRS, O_ITEMS, O_ITEMS_SMALL, O_PAT, O_LENS, NPIECES };
+
+static size_t
+blob_take(size_t *at, size_t bytes)
+{
+        const size_t o = *at;
+        *at += (bytes + 15) & ~(size_t) 15;
+        return o;
+}
+
+static int
+repair_upload_ragged(isal_hip_repair *r, const unsigned char *h_blob, size_t nblob, const size_t *offs,
+                     const uint32_t *h_tbl, size_t ntbl)
+{
+        int c, t, e;
+        unsigned row;
+        if (hipGetDevice(&r->device) != hipSuccess)
+                return ISAL_HIP_EHIP;
+        /* a row's shards are as long as that row */
+        for (c = 0; c < r->nclass; c++) {
+                const size_t stride = (size_t) (r->k + r->cls[c].nerrs);
+                const uint64_t *hp = (const uint64_t *) (h_blob + offs[c * NPIECES + O_PTRS]);
+                const int *hl = (const int *) (h_blob + offs[c * NPIECES + O_LENS]);
+                for (row = 0; row < r->cls[c].nrows; row++)
+                        if ((e = isal_hip_batch_check_ptrs(hp + row * stride, stride, (size_t) hl[row], r->device)) !=
+                            ISAL_HIP_OK)
+                                return e;
+        }
+        if (!nblob)
+                return ISAL_HIP_OK;
+        if (hipMalloc((void **) &r->d_blob, nblob) != hipSuccess ||
+            hipMalloc((void **) &r->d_tbl, ntbl) != hipSuccess)
+                return ISAL_HIP_ENOMEM;
+        if (hipMemcpy(r->d_blob, h_blob, nblob, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(r->d_tbl, h_tbl, ntbl, hipMemcpyHostToDevice) != hipSuccess)
+                return ISAL_HIP_EHIP;
+        for (c = 0; c < r->nclass; c++) {
+                rclass *cl = &r->cls[c];
+                const size_t *o = offs + c * NPIECES;
+                cl->d_ptrs = (uint64_t *) (r->d_blob + o[O_PTRS]);
+                cl->d_pat = (uint32_t *) (r->d_blob + o[O_PAT]);
+                cl->d_lens = (int *) (r->d_blob + o[O_LENS]);
+                for (t = 0; t < NTILES; t++)
+                        if (cl->nitems[t])
+                                cl->d_items[t] = (unsigned *) (r->d_blob + o[O_ITEMS + t]);
+        }
+        return ISAL_HIP_OK;
+}
+
+int
+isal_hip_repair_create_ragged(isal_hip_repair **out, int k, int m, const unsigned char *a, int nstripes,
+                              const int *lens, int max_errs, const unsigned char *nerrs, const unsigned char *errs,
+                              unsigned char *const *shards, int *bad_stripe)
+{
+        static const int tile[NTILES] = { ISAL_HIP_RAGGED_TILE, ISAL_HIP_RAGGED_TILE_SMALL };
+        isal_hip_repair *r = NULL;
+        patset ps;
+        unsigned char mark[MAX_SHARDS];
+        unsigned cnt[MAX_SHARDS + 1], base[MAX_SHARDS + 1]; /* rows of each count, their first row */
+        int32_t *s_pat = NULL;                              /* -1: a stripe that lost nothing */
+        uint32_t *first = NULL, *ord = NULL, *rstripe = NULL;
+        int *rlens = NULL;
+        size_t *offs = NULL, nblob = 0;
+        unsigned char *h_blob = NULL;
+        unsigned nrows = 0, row;
+        long long s, n;
+        int i, c, t, ret;
+
+        if (bad_stripe)
+                *bad_stripe = -1;
+        if (!out)
+                return ISAL_HIP_EINVAL;
+        *out = NULL;
+        if (k < 1 || m <= k || m > MAX_SHARDS || !a || nstripes < 1 || !lens || max_errs < 1 || max_errs > m - k ||
+            !nerrs || !errs || !shards)
+                return ISAL_HIP_EINVAL;
+
+        ret = patset_init(&ps, k, m, a, max_errs, nstripes);
+        s_pat = (int32_t *) malloc((size_t) nstripes * 4);
+        if (ret == ISAL_HIP_OK && !s_pat)
+                ret = ISAL_HIP_ENOMEM;
+        if (ret != ISAL_HIP_OK)
+                goto done;
+
+        /* 1-2: validate every stripe, find its pattern, build new patterns'
+         * tables; a stripe that lost nothing or is empty is held to the same
+         * contract */
+        memset(cnt, 0, sizeof(cnt));
+        for (s = 0; s < nstripes && ret == ISAL_HIP_OK; s++) {
+                unsigned char *const *sh = shards + (size_t) s * m;
+                if (nerrs[s] > max_errs || lens[s] < 0)
+                        ret = ISAL_HIP_EINVAL;
+                else
+                        ret = mark_errs(m, nerrs[s], errs + (size_t) s * max_errs, mark);
+                for (i = 0; i < m && ret == ISAL_HIP_OK; i++)
+                        if (!sh[i] || ((uintptr_t) sh[i] & 15))
+                                ret = ISAL_HIP_EINVAL;
+                if (ret == ISAL_HIP_OK) {
+                        s_pat[s] = -1;
+                        if (nerrs[s] && (i = patset_find(&ps, nerrs[s], mark)) < 0)
+                                ret = i;
+                        else if (nerrs[s])
+                                s_pat[s] = i;
+                        if (ret == ISAL_HIP_OK && nerrs[s] && lens[s] > 0)
+                                cnt[nerrs[s]]++;
+                }
+                if (ret != ISAL_HIP_OK && ret != ISAL_HIP_ENOMEM && bad_stripe)
+                        *bad_stripe = (int) s;
+        }
+        if (ret != ISAL_HIP_OK)
+                goto done;
+
+        r = (isal_hip_repair *) calloc(1, sizeof(*r));
+        if (!r) {
+                ret = ISAL_HIP_ENOMEM;
+                goto done;
+        }
+        r->ragged = 1;
+        r->k = k;
+        r->nstripes = nstripes;
+        r->npat = ps.npat;
+        for (c = 1; c <= max_errs; c++) {
+                base[c] = nrows;
+                nrows += cnt[c];
+                r->nclass += cnt[c] != 0;
+        }
+
+        /* 3: the rows of all classes, class after class, each class sorted by
+         * pattern (a counting sort by pattern, then a stable split by count) */
+        first = (uint32_t *) calloc((size_t) ps.npat + 1, 4);
+        ord = (uint32_t *) malloc(((size_t) nrows + 1) * 4);
+        rstripe = (uint32_t *) malloc(((size_t) nrows + 1) * 4);
+        rlens = (int *) malloc(((size_t) nrows + 1) * sizeof(int));
+        r->cls = (rclass *) calloc((size_t) r->nclass + 1, sizeof(rclass));
+        offs = (size_t *) calloc((size_t) r->nclass + 1, NPIECES * sizeof(size_t));
+        if (!first || !ord || !rstripe || !rlens || !r->cls || !offs) {
+                ret = ISAL_HIP_ENOMEM;
+                goto done;
+        }
+        for (s = 0; s < nstripes; s++)
+                if (s_pat[s] >= 0 && lens[s] > 0)
+                        first[s_pat[s] + 1]++;
+        for (i = 0; i < ps.npat; i++)
+                first[i + 1] += first[i];
+        for (s = 0; s < nstripes; s++)
+                if (s_pat[s] >= 0 && lens[s] > 0)
+                        ord[first[s_pat[s]]++] = (uint32_t) s;
+        for (row = 0; row < nrows; row++) {
+                const uint32_t st = ord[row], at = base[nerrs[st]]++;
+                rstripe[at] = st;
+                rlens[at] = lens[st];
+        }
+
+        /* the classes present, their item counts against the launch limit at
+         * the smallest tile each one uses, and their places in the blob */
+        for (c = 1, i = 0; c <= max_errs; c++) {
+                rclass *cl = &r->cls[i];
+                const int *cl_lens = rlens + (base[c] - cnt[c]);
+                if (!cnt[c])
+                        continue;
+                cl->nerrs = c;
+                cl->nrows = cnt[c];
+                for (t = 0; t < NTILES; t++) {
+                        if (!class_uses(c, t))
+                                continue;
+                        n = isal_hip_ragged_items((int) cl->nrows, cl_lens, tile[t], NULL);
+                        if (n > (long long) ISAL_HIP_RAGGED_MAX_ITEMS) {
+                                ret = ISAL_HIP_EINVAL;
+                                goto done;
+                        }
+                        cl->nitems[t] = (unsigned) n;
+                }
+                offs[i * NPIECES + O_PTRS] = blob_take(&nblob, (size_t) cl->nrows * (size_t) (k + c) * 8);
+                for (t = 0; t < NTILES; t++)
+                        offs[i * NPIECES + O_ITEMS + t] = blob_take(&nblob, (size_t) cl->nitems[t] * 8);
+                offs[i * NPIECES + O_PAT] = blob_take(&nblob, (size_t) cl->nrows * 4);
+                offs[i * NPIECES + O_LENS] = blob_take(&nblob, (size_t) cl->nrows * sizeof(int));
+                i++;
+        }
+
+        h_blob = (unsigned char *) calloc(nblob ? nblob : 1, 1);
+        if (!h_blob) {
+                ret = ISAL_HIP_ENOMEM;
+                goto done;
+        }
+        for (c = 0; c < r->nclass; c++) {
+                const rclass *cl = &r->cls[c];
+                const size_t *o = offs + c * NPIECES, stride = (size_t) (k + cl->nerrs);
+                const unsigned row0 = base[cl->nerrs] - cl->nrows;
+                uint64_t *hp = (uint64_t *) (h_blob + o[O_PTRS]);
+                uint32_t *h_pat = (uint32_t *) (h_blob + o[O_PAT]);
+                /* k survivors then the destinations in ascending order */
+                for (row = 0; row < cl->nrows; row++, hp += stride) {
+                        const uint32_t st = rstripe[row0 + row];
+                        const int32_t p = s_pat[st];
+                        unsigned char *const *sh = shards + (size_t) st * m;
+                        for (i = 0; i < k; i++)
+                                hp[i] = (uint64_t) (uintptr_t) sh[ps.surv[(size_t) p * k + i]];
+                        for (i = 0; i < cl->nerrs; i++)
+                                hp[k + i] = (uint64_t) (uintptr_t) sh[ps.keys[(size_t) p * ps.kw + 1 + i]];
+                        h_pat[row] = ps.off[p];
+                }
+                memcpy(h_blob + o[O_LENS], rlens + row0, (size_t) cl->nrows * sizeof(int));
+                for (t = 0; t < NTILES; t++)
+                        if (cl->nitems[t])
+                                (void) isal_hip_ragged_items((int) cl->nrows, rlens + row0, tile[t],
+                                                             (unsigned *) (h_blob + o[O_ITEMS + t]));
+        }
+        ret = repair_upload_ragged(r, h_blob, nblob, offs, ps.tbl, ps.tbl_dwords * 4);
+done:
+        patset_free(&ps);
+        free(s_pat);
+        free(first);
+        free(ord);
+        free(rstripe);
+        free(rlens);
+        free(offs);
+        free(h_blob);
+        if (ret != ISAL_HIP_OK) {
+                isal_hip_repair_destroy(r);
+                return ret;
+        }
+        *out = r;
+        return ISAL_HIP_OK;
+}
+
+static int
+repair_run_ragged(isal_hip_repair *r, void *stream)
+{
+        int c;
+        for (c = 0; c < r->nclass; c++) {
+                const rclass *cl = &r->cls[c];
+                if (isal_hip_launch_repair_ragged(cl->d_ptrs, r->k + cl->nerrs, cl->d_pat, r->d_tbl, cl->d_lens,
+                                                  cl->d_items[BIG], cl->nitems[BIG], cl->d_items[SMALL],
+                                                  cl->nitems[SMALL], r->k, cl->nerrs, stream))
+                        return ISAL_HIP_EHIP;
+        }
+        return ISAL_HIP_OK;
+}
+
 static int
 repair_run_impl(isal_hip_repair *r, void *stream)
 {
+        if (r->ragged)
+                return repair_run_ragged(r, stream);
         return isal_hip_launch_repair(r->d_ptrs, r->k + r->nerrs, r->d_pat, r->d_tbl, r->tbl_stride, r->len,
                                       r->k, r->nerrs, r->nstripes, stream)
                        ? ISAL_HIP_EHIP
@@ -330,6 +649,9 @@ isal_hip_repair_destroy(isal_hip_repair *r)
                 (void) hipFree(r->d_pat);
         if (r->d_tbl)
                 (void) hipFree(r->d_tbl);
+        if (r->d_blob)
+                (void) hipFree(r->d_blob);
+        free(r->cls);
         free(r);
         return ISAL_HIP_OK;
 }

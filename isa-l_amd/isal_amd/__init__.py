@@ -109,6 +109,9 @@ def lib() -> ctypes.CDLL:
             "isal_hip_decode_matrix": (i, [i, i, _u8p, i, _u8p, _u8p, _u8p]),
             "isal_hip_repair_create": (i, [ctypes.POINTER(ctypes.c_void_p), i, i, i, _u8p, i, i, _u8p, _u8pp,
                                            ctypes.POINTER(ctypes.c_int)]),
+            "isal_hip_repair_create_ragged": (i, [ctypes.POINTER(ctypes.c_void_p), i, i, _u8p, i,
+                                                  ctypes.POINTER(ctypes.c_int), i, _u8p, _u8p, _u8pp,
+                                                  ctypes.POINTER(ctypes.c_int)]),
             "isal_hip_repair_run": (i, [ctypes.c_void_p, ctypes.c_void_p]),
             "isal_hip_repair_npatterns": (i, [ctypes.c_void_p]),
             "isal_hip_repair_destroy": (i, [ctypes.c_void_p]),
@@ -423,6 +426,33 @@ class Repair:
             raise RuntimeError(f"isal_hip_repair_create failed ({rc}, stripe {bad.value})")
         self.len, self.k, self.m, self.nerrs, self.nstripes = len_, k, m, nerrs, nstripes
         self._h = h
+
+    @classmethod
+    def ragged(cls, k: int, m: int, a, lens: Sequence[int], errs: Sequence[Sequence[int]],
+               shards: Sequence) -> "Repair":
+        """isal_hip_repair_create_ragged: stripe s has shards of lens[s] bytes and
+        lost the shards errs[s] (any number from none to m - k of them, its own
+        count); shards as for Repair()."""
+        nstripes = len(lens)
+        if len(errs) != nstripes or len(shards) != nstripes * m:
+            raise ValueError("errs must hold one index sequence per stripe and shards nstripes*m")
+        ln = np.ascontiguousarray(np.array(list(lens), dtype=np.int64).astype(np.intc))
+        max_errs = max([len(e) for e in errs], default=0)
+        n = np.array([len(e) for e in errs], dtype=np.uint8)
+        e = np.zeros(max(1, nstripes * max_errs), dtype=np.uint8)
+        for s, row in enumerate(errs):
+            e[s * max_errs:s * max_errs + len(row)] = list(row)
+        h, bad = ctypes.c_void_p(), ctypes.c_int(-1)
+        rc = lib().isal_hip_repair_create_ragged(ctypes.byref(h), k, m, _p(_u8(a)), nstripes,
+                                                 ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), max_errs, _p(n),
+                                                 _p(e), _pp(shards), ctypes.byref(bad))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_repair_create_ragged failed ({rc}, stripe {bad.value})")
+        self = cls.__new__(cls)
+        self.len, self.k, self.m, self.nerrs, self.nstripes = None, k, m, max_errs, nstripes
+        self.lens = [int(x) for x in ln]
+        self._h = h
+        return self
 
     def run(self, stream: int = 0) -> None:
         rc = lib().isal_hip_repair_run(self._h, ctypes.c_void_p(stream))
