@@ -389,6 +389,49 @@ int isal_hip_scrub_create(isal_hip_scrub **out, int len, int k, int rows,
 int isal_hip_scrub_run(isal_hip_scrub *s, unsigned int *verdict, void *stream);
 int isal_hip_scrub_destroy(isal_hip_scrub *s);
 
+/*
+ * Ragged scrub: the same object for a real rebuild window, where every stripe
+ * has its OWN shard length (the ragged batch below and
+ * isal_hip_repair_create_ragged above are its neighbours: the ragged check
+ * finds the bad stripes, this names their shards, the ragged repair rebuilds
+ * them). isal_hip_scrub_run and isal_hip_scrub_destroy serve both kinds of
+ * object.
+ *   lens:   nstripes byte lengths; lens[s] is the length of every shard of
+ *           stripe s. Any value >= 0 is valid. A stripe of length 0 is neither
+ *           read nor written; its verdict is ISAL_HIP_SCRUB_CLEAN.
+ *   k, rows, gftbls, data, coding: as for isal_hip_scrub_create.
+ * For every other stripe the verdict is exactly what
+ * isal_hip_scrub_create(len = lens[s], ...) gives for that stripe alone, the
+ * two-shard imitation limit above included.
+ * Refused, all before the first HIP call and in this order, so a host without
+ * a GPU answers the same; *bad_stripe (optional) as for the other batches:
+ *   ISAL_HIP_EINVAL    NULL arguments, nstripes <= 0, k < 1, rows < 2,
+ *                      rows > isal_hip_max_rows_per_pass() or k + rows > 256
+ *                      (*bad_stripe = -1);
+ *   ISAL_HIP_EINVAL    a negative lens[s], a NULL shard pointer or one not
+ *                      16-byte aligned (those of zero-length stripes
+ *                      included); *bad_stripe names the first such stripe;
+ *   ISAL_HIP_EINVAL    more than 2^30 work items at the 4 KiB tile, the only
+ *                      tile size of this object and the limit of one launch
+ *                      (*bad_stripe = -1);
+ *   ISAL_HIP_ESINGULAR a matrix that isal_hip_scrub_ambiguity refuses.
+ * Memory kinds and device ownership as for isal_hip_batch_create; a shard must
+ * be reachable over its own stripe's length. isal_hip_scrub_run on such an
+ * object only enqueues: the fill of verdict, then ONE kernel launch
+ * (isal_hip_kernel_launches grows by 1) over 4 KiB tiles of one stripe. Every
+ * word of verdict is rewritten by each call, unless every length is 0: then
+ * the call returns 0, enqueues nothing and leaves verdict untouched. Nothing
+ * is written to the shards.
+ * Device memory besides what the uniform scrub uses: 4 bytes per stripe, and
+ * 8 bytes per 4 KiB tile of one shard.
+ * Out of scope: more than one pass of rows, the 0/1 XOR form (the plain
+ * lookup kernel, as every ragged launch), correcting in the same pass,
+ * unaligned or host-pageable shards, and any CPU route.
+ */
+int isal_hip_scrub_create_ragged(isal_hip_scrub **out, int k, int rows, const unsigned char *gftbls,
+                                 int nstripes, const int *lens, unsigned char *const *data,
+                                 unsigned char *const *coding, int *bad_stripe);
+
 /* ---- ragged batch: stripes of different lengths in one launch ------------- */
 
 /*
@@ -446,7 +489,9 @@ int isal_hip_scrub_destroy(isal_hip_scrub *s);
  * Out of scope: update, the fused checksums, the 0/1 XOR form and the
  * LDS-staged and LDS product-table wide kernels of the uniform batch (every
  * pass takes the plain lookup kernel), unaligned or host-pageable shards, any
- * CPU route, and set_tables (one object per matrix).
+ * CPU route, and set_tables (one object per matrix). Naming the corrupt shard
+ * of a stripe the check reports is isal_hip_scrub_create_ragged above, over
+ * the same lens, data and coding.
  */
 typedef struct isal_hip_ragged isal_hip_ragged;
 long long isal_hip_ragged_items(int nstripes, const int *lens, int tile, unsigned *items);

@@ -376,16 +376,18 @@ __global__ __launch_bounds__(kBlock) void ec_encode_b1(const uint64_t* __restric
 // call's device result word (kernel-argument launch). Nothing is written to
 // the shards.
 // ---------------------------------------------------------------------------
-// The verify family (verify_items, ec_verify_rag, ec_locate_v16) keeps its
-// tile body written out in each kernel. Shared as one verify_tile<P, Pol, FL>
+// The verify family (verify_items, ec_verify_rag, ec_locate_v16,
+// ec_locate_rag) keeps its tile body written out in each kernel. Shared as one verify_tile<P, Pol, FL>
 // with a sink per family (a row hook for the check, a whole-vector hook for
 // the locate), every one of the three lost occupancy or gained scratch
 // somewhere (VGPRs own -> shared): ec_verify_v16<5, EncPol<6, ..>, 0> 64 -> 72
 // and <6, EncPol<6, ..>, 0> 63 -> 71 (8 -> 7 waves per SIMD),
 // ec_verify_karg<8, EncPol<4, ..>, 1> and <8, EncPol<6, ..>, 1> 0 -> 20 bytes
 // of scratch, ec_verify_rag<5, EncPol<4, ..>> 64 -> 65 (8 -> 7),
-// ec_locate_v16<8, EncPol<4, ..>, 0> 96 -> 97 (5 -> 4). A change to the
-// kEarly rule or to the tail is made in all three.
+// ec_locate_v16<8, EncPol<4, ..>, 0> 96 -> 97 (5 -> 4). ec_locate_rag, the
+// fourth member (ec_verify_rag's item, ec_locate_v16's body), came after that
+// experiment and follows its result. A change to the kEarly rule or to the
+// tail is made in all four.
 // sbad != nullptr (a batch): each stripe's mismatches lower sbad[stripe]
 // instead, and items run in the XCD-contiguous order of the encode.
 template <int P, class Pol, int FL>
@@ -1396,6 +1398,45 @@ __global__ __launch_bounds__(kBlock, (enc_waves<P, Pol::U, kEncLUT | kEncVerify>
   }
 }
 
+// ec_locate_v16 for one item (4 KiB tiles; the ragged scrub, isal_hip_scrub.c):
+// sources at [0, k), stored rows at [k, k + P) of the stripe's pointers, every
+// load bounded by the stripe's own length; a mismatching byte column's answer
+// is folded into verdict[stripe]. Nothing is written to the shards.
+template <int P, class Pol>
+__global__ __launch_bounds__(kBlock, (enc_waves<P, Pol::U, kEncLUT | kEncVerify>())) void ec_locate_rag(
+    const uint64_t* __restrict__ ptrs, int ptr_stride, const uint2* __restrict__ items,
+    const int* __restrict__ lens, const uint32_t* __restrict__ tbl, int k, unsigned nitems,
+    const uint8_t* __restrict__ loc, unsigned* __restrict__ verdict) {
+  if (blockIdx.x >= nitems) return;
+  const RagItem it = rag_item(items, lens, nitems);
+  const uint64_t* __restrict__ sp = ptrs + static_cast<size_t>(it.stripe) * ptr_stride;
+  const int len = it.len;
+  const long long off = static_cast<long long>(it.tile) * kTile + threadIdx.x * kVec;
+  if (off + kVec <= len) {
+    constexpr bool kEarly = P <= 3;  // as verify_items: the stored rows' latency under the fold
+    uint4 st[kEarly ? P : 1];
+    if constexpr (kEarly) {
+#pragma unroll
+      for (int l = 0; l < P; ++l) st[l] = load16<kBufNT>(sp[k + l], off, len);
+    }
+    uint32_t acc[P][4];
+    accum16<P, Pol, kEncLUT>(acc, sp, tbl, k, off, len);
+    uint32_t any = 0;
+#pragma unroll
+    for (int l = 0; l < P; ++l) {
+      const uint4 e = kEarly ? st[kEarly ? l : 0] : load16<kBufNT>(sp[k + l], off, len);
+      acc[l][0] ^= e.x;
+      acc[l][1] ^= e.y;
+      acc[l][2] ^= e.z;
+      acc[l][3] ^= e.w;
+      any |= (acc[l][0] | acc[l][1]) | (acc[l][2] | acc[l][3]);
+    }
+    if (__builtin_expect(any != 0, 0)) locate_vec<P>(acc, loc, k, verdict + it.stripe);
+  } else if (off < len) {
+    locate_bytes<P>(sp, tbl, k, off, static_cast<int>(len - off), loc, verdict + it.stripe);
+  }
+}
+
 // The host builds one item table per tile size (isal_hip_internal.h).
 static_assert(enc_block<1>() * kVec == ISAL_HIP_RAGGED_TILE_SMALL &&
                   enc_block<ISAL_HIP_RAGGED_SMALL_ROWS>() * kVec == ISAL_HIP_RAGGED_TILE_SMALL &&
@@ -1923,6 +1964,33 @@ extern "C" int isal_hip_launch_verify_ragged(const uint64_t* d_ptrs, int ptr_str
         ISAL_LAUNCH((ec_verify_rag<decltype(P)::value, EncPol<decltype(U)::value, kBufNT, kBufNT, 0>>), dim3(nitems),
                     dim3(kBlock), 0, s, d_ptrs, ptr_stride, items, d_lens, p.tbl, k + p.r0, p.r0, k, nitems, bad);
       });
+    });
+    return hipSuccess;
+  });
+}
+
+// The ragged scrub's launch: verdict (nstripes words) is filled with "clean"
+// on the stream, then one ec_locate_rag launch over the 4 KiB item table (one
+// pass: rows <= 8), with the verify's load group.
+extern "C" int isal_hip_launch_locate_ragged(const uint64_t* d_ptrs, int ptr_stride, const uint32_t* d_tbl,
+                                             const int* d_lens, const unsigned* d_items, unsigned nitems, int k,
+                                             int rows, long long nstripes, const unsigned char* d_loc,
+                                             unsigned* verdict, void* stream) {
+  if (nstripes <= 0 || nitems == 0) return 0;  // every length 0
+  if (rows < 2 || rows > EC_MAX_ROWS_PER_PASS || k < 1 || nitems > kMaxItems || !d_items)
+    return static_cast<int>(hipErrorInvalidValue);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipError_t e = hipMemsetAsync(verdict, 0xff, static_cast<size_t>(nstripes) * 4, s);
+  if (e != hipSuccess) return static_cast<int>(e);
+  const uint2* items = reinterpret_cast<const uint2*>(d_items);
+  return for_passes(d_tbl, k, rows, nullptr, [&](const Pass& p) {  // one pass: rows <= 8
+    with_rows(p.P, [&](auto P) {
+      if constexpr (decltype(P)::value >= 2)  // a single row names no shard
+        with_verify_group(k, [&](auto U) {
+          ISAL_LAUNCH((ec_locate_rag<decltype(P)::value, EncPol<decltype(U)::value, kBufNT, kBufNT, 0>>),
+                      dim3(nitems), dim3(kBlock), 0, s, d_ptrs, ptr_stride, items, d_lens, p.tbl, k, nitems, d_loc,
+                      verdict);
+        });
     });
     return hipSuccess;
   });

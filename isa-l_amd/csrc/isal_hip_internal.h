@@ -291,6 +291,17 @@ int isal_hip_launch_encode_ragged(const uint64_t *d_ptrs, int ptr_stride, const 
 int isal_hip_launch_verify_ragged(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_tbl,
                                   const int *d_lens, const unsigned *d_items, unsigned nitems, int k,
                                   int rows, long long nstripes, unsigned long long *bad, void *stream);
+/* Ragged scrub (ec_kernels.hip ec_locate_rag): isal_hip_launch_locate_batch
+ * where stripe s has its own length d_lens[s], over the
+ * ISAL_HIP_RAGGED_TILE-byte item table (one pass: 2 <= rows <=
+ * EC_MAX_ROWS_PER_PASS, always the plain lookup form). verdict (device,
+ * nstripes words) is set to "clean" on the stream, then one launch of nitems
+ * workgroups; nothing is enqueued when nitems == 0. d_loc as for
+ * isal_hip_launch_locate_batch. */
+int isal_hip_launch_locate_ragged(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_tbl,
+                                  const int *d_lens, const unsigned *d_items, unsigned nitems, int k,
+                                  int rows, long long nstripes, const unsigned char *d_loc,
+                                  unsigned *verdict, void *stream);
 
 /* Ragged repair (ec_kernels.hip ec_repair_rag): one count class of
  * isal_hip_repair_create_ragged, the rows that lost `rows` shards. Pointer rows

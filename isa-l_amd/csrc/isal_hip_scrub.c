@@ -21,6 +21,13 @@
  *      non-zero coefficient, and that coefficient's inverse.
  * A scrub batch belongs to the device that was current when it was created
  * (ON_BATCH_DEVICE).
+ *
+ * The ragged scrub (isal_hip_scrub_create_ragged) is the same object where
+ * every stripe has its own length: step 1 also takes each stripe's length,
+ * the item count at the 4 KiB tile is checked against the launch limit before
+ * step 2, and the upload also builds the work-item table of the ragged batch
+ * (isal_hip_ragged_items). Its run is one ec_locate_rag launch over that table,
+ * always in the plain lookup form, so it keeps no 0/1 masks.
  */
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -39,7 +46,16 @@ struct isal_hip_scrub {
         uint32_t *d_tbl;
         unsigned char *d_loc;
         isal_hip_encmask em;
+        /* the ragged kind: per-stripe lengths and the 4 KiB item table (len unused) */
+        int ragged;
+        unsigned nitems;
+        int *d_lens;
+        unsigned *d_items;
 };
+
+/* tests/sanitize/scrub_host.c links this file without the ragged pieces */
+#pragma weak isal_hip_ragged_items
+#pragma weak isal_hip_launch_locate_ragged
 
 /* C[l][j] for j < k, the identity's column j - k beyond */
 static unsigned char
@@ -151,18 +167,29 @@ build_loc(int k, int rows, const unsigned char *gftbls, unsigned char *loc)
         }
 }
 
+/* lens: the ragged kind's (NULL for one len). Its item table (s->nitems rows)
+ * is built here, after the pointers have been classified: a batch near the
+ * item limit with unreachable shards is refused without 8 GiB of host table. */
 static int
-scrub_upload(isal_hip_scrub *s, const uint64_t *h_ptrs, const uint32_t *h_tbl, const unsigned char *h_loc)
+scrub_upload(isal_hip_scrub *s, const uint64_t *h_ptrs, const uint32_t *h_tbl, const unsigned char *h_loc,
+             const int *lens)
 {
-        const size_t nptr = (size_t) s->nstripes * (size_t) (s->k + s->rows);
+        unsigned *h_items;
+        const size_t stride = (size_t) (s->k + s->rows);
+        const size_t nptr = (size_t) s->nstripes * stride;
         const size_t ntbl = isal_hip_tables_dwords(s->k, s->rows) * 4;
         const size_t nloc = (size_t) (s->rows + 2) * (size_t) s->k;
-        int e;
+        int i, e;
         if (hipGetDevice(&s->device) != hipSuccess)
                 return ISAL_HIP_EHIP;
-        if (s->len > 0 &&
+        if (!lens && s->len > 0 &&
             (e = isal_hip_batch_check_ptrs(h_ptrs, nptr, (size_t) s->len, s->device)) != ISAL_HIP_OK)
                 return e;
+        /* a ragged stripe's shards are as long as that stripe */
+        for (i = 0; lens && i < s->nstripes; i++)
+                if (lens[i] > 0 && (e = isal_hip_batch_check_ptrs(h_ptrs + (size_t) i * stride, stride,
+                                                                  (size_t) lens[i], s->device)) != ISAL_HIP_OK)
+                        return e;
         if (hipMalloc((void **) &s->d_ptrs, nptr * 8) != hipSuccess ||
             hipMalloc((void **) &s->d_tbl, ntbl + 4) != hipSuccess ||
             hipMalloc((void **) &s->d_loc, nloc) != hipSuccess)
@@ -171,7 +198,23 @@ scrub_upload(isal_hip_scrub *s, const uint64_t *h_ptrs, const uint32_t *h_tbl, c
             hipMemcpy(s->d_tbl, h_tbl, ntbl, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(s->d_loc, h_loc, nloc, hipMemcpyHostToDevice) != hipSuccess)
                 return ISAL_HIP_EHIP;
-        return ISAL_HIP_OK;
+        if (!lens)
+                return ISAL_HIP_OK;
+        if (hipMalloc((void **) &s->d_lens, (size_t) s->nstripes * sizeof(int)) != hipSuccess)
+                return ISAL_HIP_ENOMEM;
+        if (hipMemcpy(s->d_lens, lens, (size_t) s->nstripes * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+                return ISAL_HIP_EHIP;
+        if (!s->nitems)
+                return ISAL_HIP_OK;
+        h_items = (unsigned *) malloc((size_t) s->nitems * 8);
+        if (!h_items || hipMalloc((void **) &s->d_items, (size_t) s->nitems * 8) != hipSuccess) {
+                free(h_items);
+                return ISAL_HIP_ENOMEM;
+        }
+        (void) isal_hip_ragged_items(s->nstripes, lens, ISAL_HIP_RAGGED_TILE, h_items);
+        e = hipMemcpy(s->d_items, h_items, (size_t) s->nitems * 8, hipMemcpyHostToDevice) != hipSuccess;
+        free(h_items);
+        return e ? ISAL_HIP_EHIP : ISAL_HIP_OK;
 }
 
 int
@@ -235,7 +278,87 @@ isal_hip_scrub_create(isal_hip_scrub **out, int len, int k, int rows, const unsi
         sc->k = k;
         sc->rows = rows;
         sc->nstripes = nstripes;
-        ret = scrub_upload(sc, h_ptrs, h_tbl, h_loc);
+        ret = scrub_upload(sc, h_ptrs, h_tbl, h_loc, NULL);
+done:
+        free(h_ptrs);
+        free(h_tbl);
+        free(h_loc);
+        if (ret != ISAL_HIP_OK) {
+                isal_hip_scrub_destroy(sc);
+                return ret;
+        }
+        *out = sc;
+        return ISAL_HIP_OK;
+}
+
+int
+isal_hip_scrub_create_ragged(isal_hip_scrub **out, int k, int rows, const unsigned char *gftbls, int nstripes,
+                             const int *lens, unsigned char *const *data, unsigned char *const *coding,
+                             int *bad_stripe)
+{
+        isal_hip_scrub *sc = NULL;
+        uint64_t *h_ptrs = NULL;
+        uint32_t *h_tbl = NULL;
+        unsigned char *h_loc = NULL;
+        long long s, n = 0;
+        int i, ret = ISAL_HIP_OK;
+        size_t stride;
+
+        if (bad_stripe)
+                *bad_stripe = -1;
+        if (!out)
+                return ISAL_HIP_EINVAL;
+        *out = NULL;
+        if (k < 1 || rows < 2 || rows > EC_MAX_ROWS_PER_PASS || k + rows > MAX_SHARDS || !gftbls || nstripes < 1 ||
+            !lens || !data || !coding)
+                return ISAL_HIP_EINVAL;
+        stride = (size_t) k + (size_t) rows;
+
+        h_ptrs = (uint64_t *) malloc((size_t) nstripes * stride * 8);
+        if (!h_ptrs)
+                return ISAL_HIP_ENOMEM;
+        /* 1: every stripe's length and pointers while its table row is written */
+        for (s = 0; s < nstripes && ret == ISAL_HIP_OK; s++) {
+                uint64_t *hp = h_ptrs + (size_t) s * stride;
+                for (i = 0; i < k; i++)
+                        hp[i] = (uint64_t) (uintptr_t) data[(size_t) s * k + i];
+                for (i = 0; i < rows; i++)
+                        hp[k + i] = (uint64_t) (uintptr_t) coding[(size_t) s * rows + i];
+                if (lens[s] < 0)
+                        ret = ISAL_HIP_EINVAL;
+                for (i = 0; i < (int) stride; i++)
+                        if (!hp[i] || (hp[i] & 15))
+                                ret = ISAL_HIP_EINVAL;
+                if (ret != ISAL_HIP_OK && bad_stripe)
+                        *bad_stripe = (int) s;
+        }
+        /* one launch covers every item (the only tile size here is 4 KiB) */
+        if (ret == ISAL_HIP_OK &&
+            (n = isal_hip_ragged_items(nstripes, lens, ISAL_HIP_RAGGED_TILE, NULL)) > (long long) ISAL_HIP_RAGGED_MAX_ITEMS)
+                ret = ISAL_HIP_EINVAL;
+        /* 2: two shards that explain the same syndrome cannot be told apart */
+        if (ret == ISAL_HIP_OK)
+                ret = isal_hip_scrub_ambiguity(k, rows, gftbls, NULL);
+        if (ret != ISAL_HIP_OK)
+                goto done;
+
+        /* 3: the encode's tables, the mismatch branch's tables; the item table
+         * at the upload */
+        h_tbl = (uint32_t *) malloc(isal_hip_tables_dwords(k, rows) * 4 + 4);
+        h_loc = (unsigned char *) malloc((size_t) (rows + 2) * (size_t) k);
+        sc = (isal_hip_scrub *) calloc(1, sizeof(*sc));
+        if (!h_tbl || !h_loc || !sc) {
+                ret = ISAL_HIP_ENOMEM;
+                goto done;
+        }
+        isal_hip_build_tables(k, rows, gftbls, h_tbl);
+        build_loc(k, rows, gftbls, h_loc);
+        sc->ragged = 1;
+        sc->nitems = (unsigned) n;
+        sc->k = k;
+        sc->rows = rows;
+        sc->nstripes = nstripes;
+        ret = scrub_upload(sc, h_ptrs, h_tbl, h_loc, lens);
 done:
         free(h_ptrs);
         free(h_tbl);
@@ -251,6 +374,11 @@ done:
 static int
 scrub_run_impl(isal_hip_scrub *s, unsigned int *verdict, void *stream)
 {
+        if (s->ragged)
+                return isal_hip_launch_locate_ragged(s->d_ptrs, s->k + s->rows, s->d_tbl, s->d_lens, s->d_items,
+                                                     s->nitems, s->k, s->rows, s->nstripes, s->d_loc, verdict, stream)
+                               ? ISAL_HIP_EHIP
+                               : ISAL_HIP_OK;
         return isal_hip_launch_locate_batch(s->d_ptrs, s->k + s->rows, s->d_tbl, s->len, s->k, s->rows, s->nstripes,
                                             &s->em, s->d_loc, verdict, stream)
                        ? ISAL_HIP_EHIP
@@ -276,6 +404,10 @@ isal_hip_scrub_destroy(isal_hip_scrub *s)
                 (void) hipFree(s->d_tbl);
         if (s->d_loc)
                 (void) hipFree(s->d_loc);
+        if (s->d_lens)
+                (void) hipFree(s->d_lens);
+        if (s->d_items)
+                (void) hipFree(s->d_items);
         free(s);
         return ISAL_HIP_OK;
 }

@@ -123,6 +123,9 @@ def lib() -> ctypes.CDLL:
             "isal_hip_locate_syndrome": (i, [i, i, _u8p, _u8p]),
             "isal_hip_scrub_create": (i, [ctypes.POINTER(ctypes.c_void_p), i, i, i, _u8p, i, _u8pp, _u8pp,
                                           ctypes.POINTER(ctypes.c_int)]),
+            "isal_hip_scrub_create_ragged": (i, [ctypes.POINTER(ctypes.c_void_p), i, i, _u8p, i,
+                                                 ctypes.POINTER(ctypes.c_int), _u8pp, _u8pp,
+                                                 ctypes.POINTER(ctypes.c_int)]),
             "isal_hip_scrub_run": (i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
             "isal_hip_scrub_destroy": (i, [ctypes.c_void_p]),
             "isal_hip_ragged_items": (ctypes.c_longlong, [i, ctypes.POINTER(ctypes.c_int), i,
@@ -571,6 +574,27 @@ class Scrub:
             raise RuntimeError(f"isal_hip_scrub_create failed ({rc}, stripe {bad.value})")
         self.len, self.k, self.rows, self.nstripes = len_, k, rows, nstripes
         self._h = h
+
+    @classmethod
+    def ragged(cls, k: int, rows: int, gftbls, lens: Sequence[int], data: Sequence, coding: Sequence) -> "Scrub":
+        """isal_hip_scrub_create_ragged: stripe s has shards of lens[s] bytes
+        (any length >= 0; a stripe of length 0 reads SCRUB_CLEAN); data and
+        coding as for Scrub(). One launch names the shard of every stripe."""
+        nstripes = len(lens)
+        if len(data) != nstripes * k or len(coding) != nstripes * rows:
+            raise ValueError("pointer lists must hold len(lens)*k and len(lens)*rows entries")
+        ln = np.ascontiguousarray(np.array(list(lens), dtype=np.int64).astype(np.intc))
+        h, bad = ctypes.c_void_p(), ctypes.c_int(-1)
+        rc = lib().isal_hip_scrub_create_ragged(ctypes.byref(h), k, rows, _p(gftbls), nstripes,
+                                                ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _pp(data),
+                                                _pp(coding), ctypes.byref(bad))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_scrub_create_ragged failed ({rc}, stripe {bad.value})")
+        self = cls.__new__(cls)
+        self.len, self.k, self.rows, self.nstripes = None, k, rows, nstripes
+        self.lens = [int(x) for x in ln]
+        self._h = h
+        return self
 
     def run(self, verdict, stream: int = 0) -> None:
         rc = lib().isal_hip_scrub_run(self._h, ctypes.c_void_p(addr(verdict)), ctypes.c_void_p(stream))
