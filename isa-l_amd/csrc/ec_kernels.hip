@@ -1620,6 +1620,8 @@ void overwrite_pass(hipStream_t s, const uint64_t* ptrs, int ptr_stride, const u
                     int nw, int dst0, int len, unsigned nstripes, bool commit) {
   const unsigned tiles = tiles_of(len, kUpdTile);
   const unsigned nitems = nstripes * tiles;
+  if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2)
+    fprintf(stderr, "isal_hip: kernel ec_overwrite_v16<%d, %d, %d>\n", P, commit ? 1 : 0, kUpdBlock);
   if (commit)
     ISAL_LAUNCH((ec_overwrite_v16<P, true, kUpdBlock>), dim3(grid_for(nitems)), dim3(kUpdBlock), 0, s, ptrs,
                 ptr_stride, idx, tbl0, nw, dst0, len, nitems, tiles);
@@ -1821,6 +1823,9 @@ static void verify_pass_v16(const Pass& p, unsigned grid, hipStream_t s, const u
                             int src_idx0, int dst_idx0, int len, int k, unsigned nitems, unsigned tiles,
                             unsigned long long* out, long long col0, unsigned long long* sbad) {
   with_verify_case(p.P, k, p.m.x, [&](auto P, auto U, auto FL) {
+    if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2)
+      fprintf(stderr, "isal_hip: kernel ec_verify_v16<%d, %d, %d>\n", decltype(P)::value, decltype(U)::value,
+              decltype(FL)::value);
     ISAL_LAUNCH((ec_verify_v16<decltype(P)::value, EncPol<decltype(U)::value, kBufNT, kBufNT, 0>, decltype(FL)::value>),
                 dim3(grid), dim3(kBlock), 0, s, d_ptrs, ptr_stride, src_idx0, dst_idx0 + p.r0, p.tbl, len, k, nitems,
                 tiles, out, p.r0, col0, p.m.r0m, p.m.c0m, sbad);
@@ -1887,11 +1892,15 @@ extern "C" int isal_hip_launch_locate_batch(const uint64_t* d_ptrs, int ptr_stri
         const unsigned nitems = ns * tiles;
         return for_passes(d_tbl, k, rows, em, [&](const Pass& p) {  // one pass: rows <= 8
           with_verify_case(p.P, k, p.m.x, [&](auto P, auto U, auto FL) {
-            if constexpr (decltype(P)::value >= 2)  // a single row names no shard
+            if constexpr (decltype(P)::value >= 2) {  // a single row names no shard
+              if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2)
+                fprintf(stderr, "isal_hip: kernel ec_locate_v16<%d, %d, %d>\n", decltype(P)::value,
+                        decltype(U)::value, decltype(FL)::value);
               ISAL_LAUNCH((ec_locate_v16<decltype(P)::value, EncPol<decltype(U)::value, kBufNT, kBufNT, 0>,
                                          decltype(FL)::value>),
                           dim3(nitems), dim3(kBlock), 0, s, ptrs, ptr_stride, p.tbl, len, k, nitems, tiles, p.m.r0m,
                           p.m.c0m, d_loc, verdict + s0);
+            }
           });
           return hipSuccess;
         });
@@ -1961,6 +1970,8 @@ extern "C" int isal_hip_launch_verify_ragged(const uint64_t* d_ptrs, int ptr_str
   return for_passes(d_tbl, k, rows, nullptr, [&](const Pass& p) {
     with_rows(p.P, [&](auto P) {
       with_verify_group(k, [&](auto U) {
+        if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2)
+          fprintf(stderr, "isal_hip: kernel ec_verify_rag<%d, %d>\n", decltype(P)::value, decltype(U)::value);
         ISAL_LAUNCH((ec_verify_rag<decltype(P)::value, EncPol<decltype(U)::value, kBufNT, kBufNT, 0>>), dim3(nitems),
                     dim3(kBlock), 0, s, d_ptrs, ptr_stride, items, d_lens, p.tbl, k + p.r0, p.r0, k, nitems, bad);
       });
@@ -1987,6 +1998,8 @@ extern "C" int isal_hip_launch_locate_ragged(const uint64_t* d_ptrs, int ptr_str
     with_rows(p.P, [&](auto P) {
       if constexpr (decltype(P)::value >= 2)  // a single row names no shard
         with_verify_group(k, [&](auto U) {
+          if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2)
+            fprintf(stderr, "isal_hip: kernel ec_locate_rag<%d, %d>\n", decltype(P)::value, decltype(U)::value);
           ISAL_LAUNCH((ec_locate_rag<decltype(P)::value, EncPol<decltype(U)::value, kBufNT, kBufNT, 0>>),
                       dim3(nitems), dim3(kBlock), 0, s, d_ptrs, ptr_stride, items, d_lens, p.tbl, k, nitems, d_loc,
                       verdict);
