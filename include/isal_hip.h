@@ -284,7 +284,8 @@ int isal_hip_repair_create_ragged(isal_hip_repair **out, int k, int m, const uns
  *     delta and changes no byte.
  *   Any other flag bit: ISAL_HIP_EINVAL, nothing enqueued.
  * Out of scope: write counts that differ within one object (one object per
- * count), unaligned or host-pageable shards, any CPU route, and overwrites of
+ * count; isal_hip_overwrite_create_ragged below lifts this and the single
+ * len), unaligned or host-pageable shards, any CPU route, and overwrites of
  * parity shards.
  */
 #define ISAL_HIP_OVERWRITE_COMMIT 1
@@ -296,6 +297,70 @@ int isal_hip_overwrite_create(isal_hip_overwrite **out, int len, int k, int rows
                               int *bad_stripe);
 int isal_hip_overwrite_run(isal_hip_overwrite *o, int flags, void *stream);
 int isal_hip_overwrite_destroy(isal_hip_overwrite *o);
+
+/*
+ * Ragged overwrite: the same object for a window of client writes, where
+ * every stripe has its OWN byte count and its OWN number of rewritten shards
+ * (one for a small write, several for a write that straddles shards, k for a
+ * full-stripe rewrite). isal_hip_overwrite_run (flags exactly as above) and
+ * isal_hip_overwrite_destroy serve both kinds of object.
+ *   lens:     nstripes byte counts; lens[s] >= 0 is the number of bytes
+ *             rewritten in stripe s. A sub-shard range is expressed by pointer
+ *             offsets, as above.
+ *   max_nw:   the stride of idx, old_data and new_data,
+ *             1 <= max_nw <= k <= 256.
+ *   nw:       nstripes counts, nw[s] in [0, max_nw] (ints: nw = k = 256 does
+ *             not fit a byte).
+ *   idx, old_data, new_data: entries [s*max_nw + i] for i < nw[s] are the slots
+ *             of stripe s: indices in [0, k), distinct within the stripe, in
+ *             any order. The rest of each row is ignored entirely: it may
+ *             hold any index and NULL or unaligned pointers.
+ *   gftbls, coding (coding[s*rows + l]): as for isal_hip_overwrite_create.
+ * A stripe with lens[s] == 0 or nw[s] == 0 is neither read nor written. Every
+ * other stripe ends byte-identical to what isal_hip_overwrite_create(lens[s],
+ * ..., nw[s], 1, ...) followed by a run with the same flags leaves for that
+ * stripe alone. Nothing outside [0, lens[s]) of any buffer is written; the
+ * new buffers, the data shards that are not rewritten and, without
+ * ISAL_HIP_OVERWRITE_COMMIT, the old shards are never written.
+ * Refused, all before the first HIP call and in this order, so a host without
+ * a GPU answers the same; *bad_stripe (optional) as for the other batches:
+ *   ISAL_HIP_EINVAL  NULL arguments, nstripes <= 0, k < 1, k > 256, rows < 1
+ *                    or max_nw out of range (*bad_stripe = -1);
+ *   ISAL_HIP_EINVAL  a negative lens[s] or nw[s], nw[s] > max_nw, or a bad or
+ *                    duplicate index among the first nw[s];
+ *   ISAL_HIP_EINVAL  a NULL pointer or one not 16-byte aligned among the
+ *                    stripe's 2*nw[s] + rows live pointers (stripes of zero
+ *                    length or zero count included);
+ *   ISAL_HIP_EINVAL  two of those ranges overlapping over the stripe's own
+ *                    lens[s] (ranges that touch pass, and so do equal
+ *                    pointers at lens[s] == 0); for these three *bad_stripe
+ *                    names the first stripe that fails any of them;
+ *   ISAL_HIP_EINVAL  more than 2^30 work items at the 2 KiB tile, the only
+ *                    tile size of this object and the limit of one launch
+ *                    (*bad_stripe = -1).
+ * Memory kinds and device ownership as for isal_hip_batch_create; a shard must
+ * be reachable over its own stripe's length.
+ * isal_hip_overwrite_run on such an object only enqueues: ONE kernel launch
+ * per pass of isal_hip_max_rows_per_pass() rows (counted by
+ * isal_hip_kernel_launches), whatever the mix of lengths and counts, and none
+ * when no stripe has both lens[s] > 0 and nw[s] > 0. Work items are 2 KiB
+ * tiles of one stripe. ISAL_HIP_OVERWRITE_COMMIT stores new over old in the
+ * last pass only; per stripe, two runs without it restore the parity and a
+ * second committed run changes no byte.
+ * Device memory: the pointer table (8*(2*max_nw + rows) bytes per stripe) and
+ * the index table (4*max_nw bytes per stripe) at stride max_nw, the
+ * coefficient tables, 4 bytes of length and 4 of count per stripe, and 8
+ * bytes per 2 KiB tile of one rewritten range (0.4 % of its bytes).
+ * Out of scope: overwrites of parity shards, unaligned or host-pageable
+ * shards, any CPU route, set_tables, and a fused checksum of the rewritten
+ * shards.
+ */
+int isal_hip_overwrite_create_ragged(isal_hip_overwrite **out, int k, int rows,
+                                     const unsigned char *gftbls, int nstripes, const int *lens,
+                                     int max_nw, const int *nw, const unsigned char *idx,
+                                     unsigned char *const *old_data,
+                                     unsigned char *const *new_data,
+                                     unsigned char *const *coding, int *bad_stripe);
 
 /* ---- scrub batch: the corrupt shard of each bad stripe in one pass -------- */
 

@@ -1526,15 +1526,15 @@ void launch_repair_rag(hipStream_t s, const uint64_t* ptrs, int ptr_stride, cons
 // ---------------------------------------------------------------------------
 template <int P, bool COMMIT>
 __device__ __forceinline__ void overwrite_bytes(const uint64_t* __restrict__ sp, const uint32_t* __restrict__ ip,
-                                                int nw, int dst0, const uint32_t* __restrict__ tbl0, long long off,
-                                                int nb) {
+                                                int nw, int new0, int dst0, const uint32_t* __restrict__ tbl0,
+                                                long long off, int nb) {
   for (int b = 0; b < nb; ++b) {
     uint32_t acc[P];
 #pragma unroll
     for (int l = 0; l < P; ++l) acc[l] = reinterpret_cast<const uint8_t*>(sp[dst0 + l])[off + b];
     for (int i = 0; i < nw; ++i) {
       uint8_t* o = reinterpret_cast<uint8_t*>(sp[i]) + off + b;
-      const uint8_t n = reinterpret_cast<const uint8_t*>(sp[nw + i])[off + b];
+      const uint8_t n = reinterpret_cast<const uint8_t*>(sp[new0 + i])[off + b];
       const Sel s = split(static_cast<uint32_t>(*o ^ n));
       if constexpr (COMMIT) *o = n;
       const unsigned j = static_cast<unsigned>(__builtin_amdgcn_readfirstlane(static_cast<int>(ip[i])));
@@ -1548,16 +1548,18 @@ __device__ __forceinline__ void overwrite_bytes(const uint64_t* __restrict__ sp,
 }
 
 // Slots i..i+U-1 of one stripe: all 2U loads issued before any arithmetic.
+// new0: where the new pointers start in sp (the stride of the slots, which the
+// ragged kind keeps apart from the stripe's own count).
 template <int P, int U, bool COMMIT>
 __device__ __forceinline__ void overwrite_group(uint32_t (&acc)[P][4], const uint64_t* __restrict__ sp,
-                                                const uint32_t* __restrict__ ip, int i, int nw,
+                                                const uint32_t* __restrict__ ip, int i, int new0,
                                                 const uint32_t* __restrict__ tbl0, long long off, int len) {
   uint4 x[U], n[U];
   const uint32_t* __restrict__ t[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     x[u] = load16<kBufNT>(sp[i + u], off, len);
-    n[u] = load16<kBufNT>(sp[nw + i + u], off, len);
+    n[u] = load16<kBufNT>(sp[new0 + i + u], off, len);
   }
 #pragma unroll
   for (int u = 0; u < U; ++u) {
@@ -1608,7 +1610,7 @@ __global__ __launch_bounds__(B) void ec_overwrite_v16(const uint64_t* __restrict
       for (int l = 0; l < P; ++l)
         store16<kBufNT>(sp[dst0 + l], off, make_uint4(acc[l][0], acc[l][1], acc[l][2], acc[l][3]), len);
     } else if (off < len) {
-      overwrite_bytes<P, COMMIT>(sp, ip, nw, dst0, tbl0, off, static_cast<int>(len - off));
+      overwrite_bytes<P, COMMIT>(sp, ip, nw, nw, dst0, tbl0, off, static_cast<int>(len - off));
     }
   }
 }
@@ -1628,6 +1630,72 @@ void overwrite_pass(hipStream_t s, const uint64_t* ptrs, int ptr_stride, const u
   else
     ISAL_LAUNCH((ec_overwrite_v16<P, false, kUpdBlock>), dim3(grid_for(nitems)), dim3(kUpdBlock), 0, s, ptrs,
                 ptr_stride, idx, tbl0, nw, dst0, len, nitems, tiles);
+}
+
+// ---------------------------------------------------------------------------
+// Ragged overwrite (isal_hip_overwrite.c isal_hip_overwrite_create_ragged,
+// DESIGN §3 "Ragged overwrite"): ec_overwrite_v16's body on ec_encode_rag's
+// items. Stripe s rewrites nws[s] of its max_nw slots over lens[s] bytes. Its
+// pointer row holds max_nw old pointers, max_nw new ones, then the parity
+// rows, and its index row max_nw words; the slots from nws[s] on are zero and
+// never read. The item table gives {stripe, 2 KiB tile} (a stripe with no
+// slot or no byte has no item); the length and the count are scalar loads
+// that readfirstlane pins to SGPRs, issued beside each other, so the slot loop
+// stays wave-uniform and the index, pointer and coefficient loads scalar as in
+// ec_overwrite_v16. lens[s] bounds every buffer load and store. One launch
+// serves every mix of counts: the count is a loop bound, not a template
+// argument.
+// ---------------------------------------------------------------------------
+template <int P, bool COMMIT, int B>
+__global__ __launch_bounds__(B) void ec_overwrite_rag(const uint64_t* __restrict__ ptrs, int ptr_stride,
+                                                      const uint2* __restrict__ items,
+                                                      const int* __restrict__ lens, const int* __restrict__ nws,
+                                                      const uint32_t* __restrict__ idx,
+                                                      const uint32_t* __restrict__ tbl0, int max_nw, int dst0,
+                                                      unsigned nitems) {
+  if (blockIdx.x >= nitems) return;
+  const RagItem it = rag_item(items, lens, nitems);
+  const int nw = __builtin_amdgcn_readfirstlane(nws[it.stripe]);
+  const int len = it.len;
+  const uint64_t* __restrict__ sp = ptrs + static_cast<size_t>(it.stripe) * ptr_stride;
+  const uint32_t* __restrict__ ip = idx + static_cast<size_t>(it.stripe) * max_nw;
+  const long long off = static_cast<long long>(it.tile) * (B * kVec) + threadIdx.x * kVec;
+  if (off + kVec <= len) {
+    uint32_t acc[P][4];
+#pragma unroll
+    for (int l = 0; l < P; ++l) {
+      const uint4 d = load16<kBufNT>(sp[dst0 + l], off, len);
+      acc[l][0] = d.x;
+      acc[l][1] = d.y;
+      acc[l][2] = d.z;
+      acc[l][3] = d.w;
+    }
+    int i = 0;
+    for (; i + 2 <= nw; i += 2) overwrite_group<P, 2, COMMIT>(acc, sp, ip, i, max_nw, tbl0, off, len);
+    if (i < nw) overwrite_group<P, 1, COMMIT>(acc, sp, ip, i, max_nw, tbl0, off, len);
+#pragma unroll
+    for (int l = 0; l < P; ++l)
+      store16<kBufNT>(sp[dst0 + l], off, make_uint4(acc[l][0], acc[l][1], acc[l][2], acc[l][3]), len);
+  } else if (off < len) {
+    overwrite_bytes<P, COMMIT>(sp, ip, nw, max_nw, dst0, tbl0, off, static_cast<int>(len - off));
+  }
+}
+
+static_assert(kUpdTile == ISAL_HIP_RAGGED_TILE_SMALL, "isal_hip_overwrite.c builds its item table for this tile");
+
+// One pass of P rows over nitems items, in ec_overwrite_v16's shape.
+template <int P>
+void overwrite_rag_pass(hipStream_t s, const uint64_t* ptrs, int ptr_stride, const uint2* items, const int* lens,
+                        const int* nws, const uint32_t* idx, const uint32_t* tbl0, int max_nw, int dst0,
+                        unsigned nitems, bool commit) {
+  if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2)
+    fprintf(stderr, "isal_hip: kernel ec_overwrite_rag<%d, %d, %d>\n", P, commit ? 1 : 0, kUpdBlock);
+  if (commit)
+    ISAL_LAUNCH((ec_overwrite_rag<P, true, kUpdBlock>), dim3(grid_for(nitems)), dim3(kUpdBlock), 0, s, ptrs,
+                ptr_stride, items, lens, nws, idx, tbl0, max_nw, dst0, nitems);
+  else
+    ISAL_LAUNCH((ec_overwrite_rag<P, false, kUpdBlock>), dim3(grid_for(nitems)), dim3(kUpdBlock), 0, s, ptrs,
+                ptr_stride, items, lens, nws, idx, tbl0, max_nw, dst0, nitems);
 }
 
 }  // namespace
@@ -1690,6 +1758,27 @@ extern "C" int isal_hip_launch_overwrite(const uint64_t* d_ptrs, int ptr_stride,
                         return hipSuccess;
                       });
                     });
+}
+
+// The ragged overwrite's run: one ec_overwrite_rag launch per pass of rows over
+// the 2 KiB item table, whatever the mix of lengths and counts.
+extern "C" int isal_hip_launch_overwrite_ragged(const uint64_t* d_ptrs, int ptr_stride, const uint32_t* d_idx,
+                                                const uint32_t* d_tbl, const int* d_lens, const int* d_nw,
+                                                const unsigned* d_items, unsigned nitems, int k, int rows,
+                                                int max_nw, int commit, void* stream) {
+  if (rows <= 0 || nitems == 0) return 0;  // no stripe with both a byte and a slot
+  if (k < 1 || max_nw < 1 || nitems > kMaxItems || !d_items) return static_cast<int>(hipErrorInvalidValue);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const uint2* items = reinterpret_cast<const uint2*>(d_items);
+  return for_passes(d_tbl, k, rows, nullptr, [&](const Pass& p) {
+    // new goes over old only once every row of the stripe has seen the delta
+    const bool last = commit && p.r0 + p.P == rows;
+    with_rows(p.P, [&](auto P) {
+      overwrite_rag_pass<decltype(P)::value>(s, d_ptrs, ptr_stride, items, d_lens, d_nw, d_idx, p.tbl, max_nw,
+                                             2 * max_nw + p.r0, nitems, last);
+    });
+    return hipSuccess;
+  });
 }
 
 // ISAL_HIP_KARG_NARROW: 1 = always the 4-byte-lane kernel, 0 = never;

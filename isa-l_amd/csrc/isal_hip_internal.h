@@ -316,6 +316,20 @@ int isal_hip_launch_repair_ragged(const uint64_t *d_ptrs, int ptr_stride, const 
                                   unsigned nitems, const unsigned *d_items_small, unsigned nitems_small,
                                   int k, int rows, void *stream);
 
+/* Ragged overwrite (ec_kernels.hip ec_overwrite_rag): isal_hip_launch_overwrite
+ * where stripe s has its own length d_lens[s] and its own count d_nw[s] <=
+ * max_nw. Pointer rows are max_nw old shards, max_nw new ones, then rows parity
+ * rows (ptr_stride = 2 * max_nw + rows, every live pointer 16-byte aligned);
+ * d_idx rows are max_nw words; the entries from d_nw[s] on are zero and never
+ * read. Items are {stripe, tile} pairs of the ISAL_HIP_RAGGED_TILE_SMALL-byte
+ * tile, none for a stripe without a byte or a slot. One launch per pass,
+ * commit as for isal_hip_launch_overwrite; nothing is enqueued when nitems
+ * == 0. */
+int isal_hip_launch_overwrite_ragged(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_idx,
+                                     const uint32_t *d_tbl, const int *d_lens, const int *d_nw,
+                                     const unsigned *d_items, unsigned nitems, int k, int rows, int max_nw,
+                                     int commit, void *stream);
+
 /* Kernel registry (isal_hip_selftest_kernels): every kernel a launcher can
  * launch registers its host handle and a name when the library loads
  * (ec_device.h ISAL_LAUNCH). */

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Sequence
+from typing import Optional, Sequence
 
 import numpy as np
 
@@ -117,6 +117,9 @@ def lib() -> ctypes.CDLL:
             "isal_hip_repair_destroy": (i, [ctypes.c_void_p]),
             "isal_hip_overwrite_create": (i, [ctypes.POINTER(ctypes.c_void_p), i, i, i, _u8p, i, i, _u8p, _u8pp, _u8pp,
                                               _u8pp, ctypes.POINTER(ctypes.c_int)]),
+            "isal_hip_overwrite_create_ragged": (i, [ctypes.POINTER(ctypes.c_void_p), i, i, _u8p, i,
+                                                     ctypes.POINTER(ctypes.c_int), i, ctypes.POINTER(ctypes.c_int),
+                                                     _u8p, _u8pp, _u8pp, _u8pp, ctypes.POINTER(ctypes.c_int)]),
             "isal_hip_overwrite_run": (i, [ctypes.c_void_p, i, ctypes.c_void_p]),
             "isal_hip_overwrite_destroy": (i, [ctypes.c_void_p]),
             "isal_hip_scrub_ambiguity": (i, [i, i, _u8p, ctypes.POINTER(ctypes.c_int)]),
@@ -504,6 +507,47 @@ class Overwrite:
             raise RuntimeError(f"isal_hip_overwrite_create failed ({rc}, stripe {bad.value})")
         self.len, self.k, self.rows, self.nw, self.nstripes = len_, k, rows, nw, nstripes
         self._h = h
+
+    @classmethod
+    def ragged(cls, k: int, rows: int, gftbls, lens: Sequence[int], idx: Sequence[Sequence[int]],
+               old_data: Sequence[Sequence], new_data: Sequence[Sequence], coding: Sequence, *,
+               max_nw: Optional[int] = None, pad_idx: int = 0, pad_ptr=0) -> "Overwrite":
+        """isal_hip_overwrite_create_ragged: stripe s rewrites lens[s] bytes of
+        the data shards idx[s] (any number from none to k of them, its own
+        count), from old_data[s][i] to new_data[s][i]; coding as for
+        Overwrite(). The rows are padded to the stride max_nw (default: the
+        longest idx[s], at least 1) with pad_idx and pad_ptr, which the library
+        ignores. One launch per pass serves every mix of lengths and counts."""
+        nstripes = len(lens)
+        if (len(idx) != nstripes or len(old_data) != nstripes or len(new_data) != nstripes
+                or len(coding) != nstripes * rows):
+            raise ValueError("idx, old_data and new_data must hold one sequence per stripe and coding nstripes*rows")
+        if any(len(old_data[s]) != len(idx[s]) or len(new_data[s]) != len(idx[s]) for s in range(nstripes)):
+            raise ValueError("old_data[s] and new_data[s] must hold one entry per index of idx[s]")
+        if max_nw is None:
+            max_nw = max([len(x) for x in idx] + [1])
+        if any(len(x) > max_nw for x in idx):
+            raise ValueError("a stripe has more than max_nw slots")
+        ln = np.ascontiguousarray(np.array(list(lens), dtype=np.int64).astype(np.intc))
+        n = np.ascontiguousarray(np.array([len(x) for x in idx], dtype=np.intc))
+        ix = np.full(max(1, nstripes * max_nw), pad_idx, dtype=np.uint8)
+        old, new = [pad_ptr] * (nstripes * max_nw), [pad_ptr] * (nstripes * max_nw)
+        for s, row in enumerate(idx):
+            ix[s * max_nw:s * max_nw + len(row)] = list(row)
+            old[s * max_nw:s * max_nw + len(row)] = list(old_data[s])
+            new[s * max_nw:s * max_nw + len(row)] = list(new_data[s])
+        h, bad = ctypes.c_void_p(), ctypes.c_int(-1)
+        ip = ctypes.POINTER(ctypes.c_int)
+        rc = lib().isal_hip_overwrite_create_ragged(ctypes.byref(h), k, rows, _p(gftbls), nstripes,
+                                                    ln.ctypes.data_as(ip), max_nw, n.ctypes.data_as(ip), _p(ix),
+                                                    _pp(old), _pp(new), _pp(coding), ctypes.byref(bad))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_overwrite_create_ragged failed ({rc}, stripe {bad.value})")
+        self = cls.__new__(cls)
+        self.len, self.k, self.rows, self.nw, self.nstripes = None, k, rows, max_nw, nstripes
+        self.lens, self.nws = [int(x) for x in ln], [int(x) for x in n]
+        self._h = h
+        return self
 
     def run(self, commit: bool = False, stream: int = 0) -> None:
         rc = lib().isal_hip_overwrite_run(self._h, OVERWRITE_COMMIT if commit else 0, ctypes.c_void_p(stream))
