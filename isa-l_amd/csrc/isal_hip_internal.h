@@ -239,6 +239,27 @@ void isal_hip_dev_leave(int prev);
  * ISAL_HIP_EINVAL (NULL, pageable) or ISAL_HIP_EDEVICE (another GPU's). */
 int isal_hip_batch_check_ptrs(const uint64_t *ptrs, size_t n, size_t len, int dev);
 
+/* ---- what every stripe object's create does (isal_hip_objects.c): the
+ * repair, overwrite, scrub and ragged batches ------------------------------ */
+#define MAX_SHARDS 256 /* shard indices are bytes */
+/* The n shard pointers p[] as a row of a pointer table (row may be NULL: the
+ * check alone). ISAL_HIP_EINVAL unless every one is set and 16-byte aligned;
+ * the whole row is written either way. */
+int isal_hip_obj_ptr_row(uint64_t *row, unsigned char *const *p, size_t n);
+/* isal_hip_batch_check_ptrs over a table of nrows rows of `stride` pointers:
+ * the whole table at once over len bytes (lens == NULL; nothing when len ==
+ * 0), or row by row over lens[row] bytes, rows of length 0 skipped. */
+int isal_hip_obj_reach(const uint64_t *ptrs, size_t nrows, size_t stride, size_t len, const int *lens, int dev);
+/* *d = a fresh device allocation of bytes + pad holding the bytes at h.
+ * ISAL_HIP_ENOMEM when the allocation fails, ISAL_HIP_EHIP when the copy does
+ * (*d is then still set: the object's destroy drops it). */
+int isal_hip_obj_put(void *d, const void *h, size_t bytes, size_t pad);
+/* hipFree(d) unless d is NULL */
+void isal_hip_obj_drop(void *d);
+/* *d = the device copy of the nitems rows isal_hip_ragged_items builds for
+ * these lengths and this tile size; nothing when nitems == 0. */
+int isal_hip_obj_put_items(unsigned **d, int nstripes, const int *lens, int tile, unsigned nitems);
+
 /* Repair (ec_kernels.hip ec_repair_v16): the vector encode over nrows rows of
  * a pointer table (k survivors then rows destinations, stride ptr_stride,
  * every shard 16-byte aligned) where row r takes the coefficient tables of
@@ -284,6 +305,21 @@ int isal_hip_launch_locate_batch(const uint64_t *d_ptrs, int ptr_stride, const u
 #define ISAL_HIP_RAGGED_TILE_SMALL 2048
 #define ISAL_HIP_RAGGED_SMALL_ROWS 2
 #define ISAL_HIP_RAGGED_MAX_ITEMS (1u << 30) /* ec_kernels.hip kMaxItems */
+/* the item tables of an object, by tile size */
+enum { TILE_BIG, TILE_SMALL, NTILES };
+static inline int
+isal_hip_tile_bytes(int t)
+{
+        return t == TILE_SMALL ? ISAL_HIP_RAGGED_TILE_SMALL : ISAL_HIP_RAGGED_TILE;
+}
+/* whether some pass of an encode of `rows` rows runs the small tile: only the
+ * last pass can be short */
+static inline int
+isal_hip_uses_small_tile(int rows)
+{
+        const int last = rows % EC_MAX_ROWS_PER_PASS;
+        return last >= 1 && last <= ISAL_HIP_RAGGED_SMALL_ROWS;
+}
 int isal_hip_launch_encode_ragged(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_tbl,
                                   const int *d_lens, const unsigned *d_items, unsigned nitems,
                                   const unsigned *d_items_small, unsigned nitems_small, int k, int rows,

@@ -11,13 +11,14 @@
  * per tile size its passes use.
  *
  * Host side, in this order (everything before the first HIP call is pure
- * arithmetic and returns the same codes on a host without a GPU):
+ * arithmetic and returns the same codes on a host without a GPU; the steps
+ * every stripe object shares are isal_hip_objects.c's):
  *   1. counts, then per stripe its length (>= 0) and every shard pointer
  *      (non-NULL, 16-byte aligned) while the pointer table (per stripe k
  *      sources then rows parity rows) is written;
  *   2. the item count at the smallest tile against the launch limit;
  *   3. gftbls becomes the encode's device coefficient tables; the item tables
- *      are built.
+ *      are built at the upload, once the shards are known to be reachable.
  * A ragged batch belongs to the device that was current when it was created
  * (ON_BATCH_DEVICE).
  */
@@ -30,17 +31,13 @@
 #include "isal_hip.h"
 #include "isal_hip_internal.h"
 
-#define MAX_SHARDS 256 /* shard indices are bytes */
-
-enum { BIG, SMALL, NTABLES }; /* ISAL_HIP_RAGGED_TILE, ISAL_HIP_RAGGED_TILE_SMALL */
-
 struct isal_hip_ragged {
         int k, rows, nstripes, device;
-        unsigned nitems[NTABLES];
+        unsigned nitems[NTILES];
         uint64_t *d_ptrs;
         uint32_t *d_tbl;
         int *d_lens;
-        unsigned *d_items[NTABLES];
+        unsigned *d_items[NTILES];
 };
 
 long long
@@ -65,60 +62,34 @@ isal_hip_ragged_items(int nstripes, const int *lens, int tile, unsigned *items)
         return n;
 }
 
-/* whether some encode pass of rows parity rows runs the small tiles */
+/* The item tables (r->nitems[] rows) are built here, after the pointers have
+ * been classified, as every ragged object does. */
 static int
-uses_small_tiles(int rows)
+ragged_upload(isal_hip_ragged *r, const uint64_t *h_ptrs, const uint32_t *h_tbl, const int *lens)
 {
-        const int last = rows % EC_MAX_ROWS_PER_PASS;
-        return last >= 1 && last <= ISAL_HIP_RAGGED_SMALL_ROWS;
-}
-
-static int
-ragged_upload(isal_hip_ragged *r, const uint64_t *h_ptrs, const uint32_t *h_tbl, const int *lens,
-              unsigned *const h_items[NTABLES])
-{
-        const size_t stride = (size_t) (r->k + r->rows);
-        const size_t nptr = (size_t) r->nstripes * stride;
-        const size_t ntbl = isal_hip_tables_dwords(r->k, r->rows) * 4;
-        int s, t, e;
+        const size_t stride = (size_t) (r->k + r->rows), nstripes = (size_t) r->nstripes;
+        int t, e;
         if (hipGetDevice(&r->device) != hipSuccess)
                 return ISAL_HIP_EHIP;
-        /* a stripe's shards are as long as that stripe */
-        for (s = 0; s < r->nstripes; s++)
-                if (lens[s] > 0 && (e = isal_hip_batch_check_ptrs(h_ptrs + (size_t) s * stride, stride, (size_t) lens[s],
-                                                                  r->device)) != ISAL_HIP_OK)
-                        return e;
-        if (hipMalloc((void **) &r->d_ptrs, nptr * 8) != hipSuccess ||
-            hipMalloc((void **) &r->d_tbl, ntbl) != hipSuccess ||
-            hipMalloc((void **) &r->d_lens, (size_t) r->nstripes * sizeof(int)) != hipSuccess)
-                return ISAL_HIP_ENOMEM;
-        if (hipMemcpy(r->d_ptrs, h_ptrs, nptr * 8, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(r->d_tbl, h_tbl, ntbl, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(r->d_lens, lens, (size_t) r->nstripes * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
-                return ISAL_HIP_EHIP;
-        for (t = 0; t < NTABLES; t++) {
-                const size_t n = (size_t) r->nitems[t] * 8;
-                if (!n)
-                        continue;
-                if (hipMalloc((void **) &r->d_items[t], n) != hipSuccess)
-                        return ISAL_HIP_ENOMEM;
-                if (hipMemcpy(r->d_items[t], h_items[t], n, hipMemcpyHostToDevice) != hipSuccess)
-                        return ISAL_HIP_EHIP;
-        }
-        return ISAL_HIP_OK;
+        if ((e = isal_hip_obj_reach(h_ptrs, nstripes, stride, 0, lens, r->device)) != ISAL_HIP_OK ||
+            (e = isal_hip_obj_put(&r->d_ptrs, h_ptrs, nstripes * stride * 8, 0)) != ISAL_HIP_OK ||
+            (e = isal_hip_obj_put(&r->d_tbl, h_tbl, isal_hip_tables_dwords(r->k, r->rows) * 4, 0)) != ISAL_HIP_OK ||
+            (e = isal_hip_obj_put(&r->d_lens, lens, nstripes * sizeof(int), 0)) != ISAL_HIP_OK)
+                return e;
+        for (t = 0; t < NTILES && e == ISAL_HIP_OK; t++)
+                e = isal_hip_obj_put_items(&r->d_items[t], r->nstripes, lens, isal_hip_tile_bytes(t), r->nitems[t]);
+        return e;
 }
 
 int
 isal_hip_ragged_create(isal_hip_ragged **out, int k, int rows, const unsigned char *gftbls, int nstripes,
                        const int *lens, unsigned char *const *data, unsigned char *const *coding, int *bad_stripe)
 {
-        static const int tile[NTABLES] = { ISAL_HIP_RAGGED_TILE, ISAL_HIP_RAGGED_TILE_SMALL };
         isal_hip_ragged *r = NULL;
         uint64_t *h_ptrs = NULL;
         uint32_t *h_tbl = NULL;
-        unsigned *h_items[NTABLES] = { NULL, NULL };
-        long long s, n;
-        int i, t, ret = ISAL_HIP_OK;
+        long long s;
+        int t, ret = ISAL_HIP_OK;
         size_t stride;
 
         if (bad_stripe)
@@ -136,15 +107,9 @@ isal_hip_ragged_create(isal_hip_ragged **out, int k, int rows, const unsigned ch
         /* 1: every stripe's length and pointers while its table row is written */
         for (s = 0; s < nstripes && ret == ISAL_HIP_OK; s++) {
                 uint64_t *hp = h_ptrs + (size_t) s * stride;
-                for (i = 0; i < k; i++)
-                        hp[i] = (uint64_t) (uintptr_t) data[(size_t) s * k + i];
-                for (i = 0; i < rows; i++)
-                        hp[k + i] = (uint64_t) (uintptr_t) coding[(size_t) s * rows + i];
-                if (lens[s] < 0)
+                if (isal_hip_obj_ptr_row(hp, data + (size_t) s * k, (size_t) k) != ISAL_HIP_OK ||
+                    isal_hip_obj_ptr_row(hp + k, coding + (size_t) s * rows, (size_t) rows) != ISAL_HIP_OK || lens[s] < 0)
                         ret = ISAL_HIP_EINVAL;
-                for (i = 0; i < (int) stride; i++)
-                        if (!hp[i] || (hp[i] & 15))
-                                ret = ISAL_HIP_EINVAL;
                 if (ret != ISAL_HIP_OK && bad_stripe)
                         *bad_stripe = (int) s;
         }
@@ -156,7 +121,8 @@ isal_hip_ragged_create(isal_hip_ragged **out, int k, int rows, const unsigned ch
         if (ret != ISAL_HIP_OK)
                 goto done;
 
-        /* 3: the encode's tables, one item table per tile size in use */
+        /* 3: the encode's tables, one item table per tile size in use (built
+         * at the upload) */
         h_tbl = (uint32_t *) malloc(isal_hip_tables_dwords(k, rows) * 4);
         r = (isal_hip_ragged *) calloc(1, sizeof(*r));
         if (!h_tbl || !r) {
@@ -167,26 +133,13 @@ isal_hip_ragged_create(isal_hip_ragged **out, int k, int rows, const unsigned ch
         r->k = k;
         r->rows = rows;
         r->nstripes = nstripes;
-        for (t = 0; t < NTABLES; t++) {
-                if (t == SMALL && !uses_small_tiles(rows))
-                        continue;
-                n = isal_hip_ragged_items(nstripes, lens, tile[t], NULL);
-                r->nitems[t] = (unsigned) n;
-                if (!n)
-                        continue;
-                h_items[t] = (unsigned *) malloc((size_t) n * 8);
-                if (!h_items[t]) {
-                        ret = ISAL_HIP_ENOMEM;
-                        goto done;
-                }
-                (void) isal_hip_ragged_items(nstripes, lens, tile[t], h_items[t]);
-        }
-        ret = ragged_upload(r, h_ptrs, h_tbl, lens, h_items);
+        for (t = 0; t < NTILES; t++)
+                if (t == TILE_BIG || isal_hip_uses_small_tile(rows))
+                        r->nitems[t] = (unsigned) isal_hip_ragged_items(nstripes, lens, isal_hip_tile_bytes(t), NULL);
+        ret = ragged_upload(r, h_ptrs, h_tbl, lens);
 done:
         free(h_ptrs);
         free(h_tbl);
-        for (t = 0; t < NTABLES; t++)
-                free(h_items[t]);
         if (ret != ISAL_HIP_OK) {
                 isal_hip_ragged_destroy(r);
                 return ret;
@@ -198,9 +151,9 @@ done:
 static int
 ragged_encode_impl(isal_hip_ragged *r, void *stream)
 {
-        return isal_hip_launch_encode_ragged(r->d_ptrs, r->k + r->rows, r->d_tbl, r->d_lens, r->d_items[BIG],
-                                             r->nitems[BIG], r->d_items[SMALL], r->nitems[SMALL], r->k, r->rows,
-                                             stream)
+        return isal_hip_launch_encode_ragged(r->d_ptrs, r->k + r->rows, r->d_tbl, r->d_lens, r->d_items[TILE_BIG],
+                                             r->nitems[TILE_BIG], r->d_items[TILE_SMALL], r->nitems[TILE_SMALL],
+                                             r->k, r->rows, stream)
                        ? ISAL_HIP_EHIP
                        : ISAL_HIP_OK;
 }
@@ -214,8 +167,8 @@ isal_hip_ragged_encode(isal_hip_ragged *r, void *stream)
 static int
 ragged_check_impl(isal_hip_ragged *r, unsigned long long *bad, void *stream)
 {
-        return isal_hip_launch_verify_ragged(r->d_ptrs, r->k + r->rows, r->d_tbl, r->d_lens, r->d_items[BIG],
-                                             r->nitems[BIG], r->k, r->rows, r->nstripes, bad, stream)
+        return isal_hip_launch_verify_ragged(r->d_ptrs, r->k + r->rows, r->d_tbl, r->d_lens, r->d_items[TILE_BIG],
+                                             r->nitems[TILE_BIG], r->k, r->rows, r->nstripes, bad, stream)
                        ? ISAL_HIP_EHIP
                        : ISAL_HIP_OK;
 }
@@ -234,15 +187,11 @@ isal_hip_ragged_destroy(isal_hip_ragged *r)
         int t;
         if (!r)
                 return ISAL_HIP_OK;
-        if (r->d_ptrs)
-                (void) hipFree(r->d_ptrs);
-        if (r->d_tbl)
-                (void) hipFree(r->d_tbl);
-        if (r->d_lens)
-                (void) hipFree(r->d_lens);
-        for (t = 0; t < NTABLES; t++)
-                if (r->d_items[t])
-                        (void) hipFree(r->d_items[t]);
+        isal_hip_obj_drop(r->d_ptrs);
+        isal_hip_obj_drop(r->d_tbl);
+        isal_hip_obj_drop(r->d_lens);
+        for (t = 0; t < NTILES; t++)
+                isal_hip_obj_drop(r->d_items[t]);
         free(r);
         return ISAL_HIP_OK;
 }

@@ -4,15 +4,17 @@
  * kernel launch per pass of up to EC_MAX_ROWS_PER_PASS rows.
  *
  * Host side, in this order (everything before the first HIP call is pure
- * arithmetic and returns the same codes on a host without a GPU):
- *   1. each stripe's erasure set is ordered and looked up in a hash table of
- *      the distinct patterns seen so far;
+ * arithmetic and returns the same codes on a host without a GPU; the steps
+ * every stripe object shares are isal_hip_objects.c's):
+ *   1. each stripe's erasure set and shard pointers (non-NULL, 16-byte
+ *      aligned) are checked, the set is ordered and looked up in a hash table
+ *      of the distinct patterns seen so far (stripe_pattern, both creates);
  *   2. a new pattern gets its recovery rows (isal_hip_decode_matrix) and its
  *      device coefficient tables, isal_hip_tables_dwords(k, nerrs) dwords at
  *      index * stride of one array;
  *   3. the pointer table (per stripe k survivors then nerrs destinations, the
- *      batch's shape) is written with its rows sorted by pattern, beside a
- *      pattern index per row: neighbouring workgroups then read the same
+ *      batch's shape, pattern_row) is written with its rows sorted by
+ *      pattern, beside a pattern index per row: neighbouring workgroups then read the same
  *      coefficient lines (ec_kernels.hip ec_repair_v16).
  * A repair batch belongs to the device that was current when it was created
  * (ON_BATCH_DEVICE).
@@ -37,10 +39,6 @@
 #include "isal_hip.h"
 #include "isal_hip_internal.h"
 
-#define MAX_SHARDS 256 /* shard indices are bytes */
-
-enum { BIG, SMALL, NTILES }; /* ISAL_HIP_RAGGED_TILE, ISAL_HIP_RAGGED_TILE_SMALL */
-
 /* one count class of a ragged repair; the device pointers lie in d_blob */
 typedef struct {
         int nerrs;
@@ -61,10 +59,6 @@ struct isal_hip_repair {
         rclass *cls;
         unsigned char *d_blob;
 };
-
-/* tests/sanitize/repair_host.c links this file without the ragged pieces */
-#pragma weak isal_hip_ragged_items
-#pragma weak isal_hip_launch_repair_ragged
 
 /* errs in range and distinct; mark[] (MAX_SHARDS bytes) receives the set */
 static int
@@ -245,26 +239,53 @@ patset_find(patset *ps, int nerrs, const unsigned char *mark)
         return ps->npat++;
 }
 
+/* One stripe's step of both creates: its length and count, its erasure set,
+ * its m shard pointers (non-NULL, 16-byte aligned), then its pattern, added
+ * when new, into *pat (untouched for a stripe that lost nothing). The stripe
+ * is named in *bad_stripe unless memory ran out, which is no stripe's fault. */
+static int
+stripe_pattern(patset *ps, long long s, int len, int nerrs, const unsigned char *errs, unsigned char *const *sh,
+               int32_t *pat, int *bad_stripe)
+{
+        unsigned char mark[MAX_SHARDS];
+        int n, ret = len < 0 || nerrs >= ps->kw ? ISAL_HIP_EINVAL : mark_errs(ps->m, nerrs, errs, mark);
+        if (ret == ISAL_HIP_OK)
+                ret = isal_hip_obj_ptr_row(NULL, sh, (size_t) ps->m);
+        if (ret == ISAL_HIP_OK && nerrs) {
+                if ((n = patset_find(ps, nerrs, mark)) < 0)
+                        ret = n;
+                else
+                        *pat = n;
+        }
+        if (ret != ISAL_HIP_OK && ret != ISAL_HIP_ENOMEM && bad_stripe)
+                *bad_stripe = (int) s;
+        return ret;
+}
+
+/* One row of a pointer table: of the stripe's m shards sh, pattern p's k
+ * survivors, then its nerrs destinations in ascending order. */
+static void
+pattern_row(uint64_t *hp, const patset *ps, int p, int nerrs, unsigned char *const *sh)
+{
+        int i;
+        for (i = 0; i < ps->k; i++)
+                hp[i] = (uint64_t) (uintptr_t) sh[ps->surv[(size_t) p * ps->k + i]];
+        for (i = 0; i < nerrs; i++)
+                hp[ps->k + i] = (uint64_t) (uintptr_t) sh[ps->keys[(size_t) p * ps->kw + 1 + i]];
+}
+
 static int
 repair_upload(isal_hip_repair *r, const uint64_t *h_ptrs, const uint32_t *h_pat, const uint32_t *h_tbl)
 {
-        const size_t nptr = (size_t) r->nstripes * (size_t) (r->k + r->nerrs);
-        const size_t ntbl = (size_t) r->npat * r->tbl_stride * 4;
+        const size_t nstripes = (size_t) r->nstripes, stride = (size_t) (r->k + r->nerrs);
         int e;
         if (hipGetDevice(&r->device) != hipSuccess)
                 return ISAL_HIP_EHIP;
-        if (r->len > 0 &&
-            (e = isal_hip_batch_check_ptrs(h_ptrs, nptr, (size_t) r->len, r->device)) != ISAL_HIP_OK)
+        if ((e = isal_hip_obj_reach(h_ptrs, nstripes, stride, (size_t) r->len, NULL, r->device)) != ISAL_HIP_OK ||
+            (e = isal_hip_obj_put(&r->d_ptrs, h_ptrs, nstripes * stride * 8, 0)) != ISAL_HIP_OK ||
+            (e = isal_hip_obj_put(&r->d_pat, h_pat, nstripes * 4, 0)) != ISAL_HIP_OK)
                 return e;
-        if (hipMalloc((void **) &r->d_ptrs, nptr * 8) != hipSuccess ||
-            hipMalloc((void **) &r->d_pat, (size_t) r->nstripes * 4) != hipSuccess ||
-            hipMalloc((void **) &r->d_tbl, ntbl) != hipSuccess)
-                return ISAL_HIP_ENOMEM;
-        if (hipMemcpy(r->d_ptrs, h_ptrs, nptr * 8, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(r->d_pat, h_pat, (size_t) r->nstripes * 4, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(r->d_tbl, h_tbl, ntbl, hipMemcpyHostToDevice) != hipSuccess)
-                return ISAL_HIP_EHIP;
-        return ISAL_HIP_OK;
+        return isal_hip_obj_put(&r->d_tbl, h_tbl, (size_t) r->npat * r->tbl_stride * 4, 0);
 }
 
 int
@@ -274,11 +295,11 @@ isal_hip_repair_create(isal_hip_repair **out, int len, int k, int m, const unsig
 {
         isal_hip_repair *r = NULL;
         patset ps;
-        unsigned char mark[MAX_SHARDS];
-        uint32_t *s_pat = NULL, *h_pat = NULL, *first = NULL;
+        int32_t *s_pat = NULL;
+        uint32_t *h_pat = NULL, *first = NULL;
         uint64_t *h_ptrs = NULL;
         long long s;
-        int i, n, ret = ISAL_HIP_OK;
+        int i, ret = ISAL_HIP_OK;
         size_t stride;
 
         if (bad_stripe)
@@ -292,28 +313,16 @@ isal_hip_repair_create(isal_hip_repair **out, int len, int k, int m, const unsig
         stride = (size_t) k + (size_t) nerrs;
 
         ret = patset_init(&ps, k, m, a, nerrs, nstripes);
-        s_pat = (uint32_t *) malloc((size_t) nstripes * 4);
+        s_pat = (int32_t *) malloc((size_t) nstripes * 4);
         if (ret == ISAL_HIP_OK && !s_pat)
                 ret = ISAL_HIP_ENOMEM;
         if (ret != ISAL_HIP_OK)
                 goto done;
 
         /* 1-2: validate every stripe, find its pattern, build new patterns' tables */
-        for (s = 0; s < nstripes && ret == ISAL_HIP_OK; s++) {
-                unsigned char *const *sh = shards + (size_t) s * m;
-                ret = mark_errs(m, nerrs, errs + (size_t) s * nerrs, mark);
-                for (i = 0; i < m && ret == ISAL_HIP_OK; i++)
-                        if (!sh[i] || ((uintptr_t) sh[i] & 15))
-                                ret = ISAL_HIP_EINVAL;
-                if (ret == ISAL_HIP_OK) {
-                        if ((n = patset_find(&ps, nerrs, mark)) < 0)
-                                ret = n;
-                        else
-                                s_pat[s] = (uint32_t) n;
-                }
-                if (ret != ISAL_HIP_OK && ret != ISAL_HIP_ENOMEM && bad_stripe)
-                        *bad_stripe = (int) s;
-        }
+        for (s = 0; s < nstripes && ret == ISAL_HIP_OK; s++)
+                ret = stripe_pattern(&ps, s, len, nerrs, errs + (size_t) s * nerrs, shards + (size_t) s * m, &s_pat[s],
+                                     bad_stripe);
         if (ret != ISAL_HIP_OK)
                 goto done;
 
@@ -332,13 +341,8 @@ isal_hip_repair_create(isal_hip_repair **out, int len, int k, int m, const unsig
         for (i = 0; i < ps.npat; i++)
                 first[i + 1] += first[i];
         for (s = 0; s < nstripes; s++) {
-                const uint32_t p = s_pat[s], row = first[p]++;
-                unsigned char *const *sh = shards + (size_t) s * m;
-                uint64_t *hp = h_ptrs + (size_t) row * stride;
-                for (i = 0; i < k; i++)
-                        hp[i] = (uint64_t) (uintptr_t) sh[ps.surv[(size_t) p * k + i]];
-                for (i = 0; i < nerrs; i++)
-                        hp[k + i] = (uint64_t) (uintptr_t) sh[ps.keys[(size_t) p * ps.kw + 1 + i]];
+                const uint32_t p = (uint32_t) s_pat[s], row = first[p]++;
+                pattern_row(h_ptrs + (size_t) row * stride, &ps, (int) p, nerrs, shards + (size_t) s * m);
                 h_pat[row] = p;
         }
         r->len = len;
@@ -369,9 +373,8 @@ done:
 static int
 class_uses(int nerrs, int t)
 {
-        const int last = nerrs % EC_MAX_ROWS_PER_PASS;
-        const int small = last >= 1 && last <= ISAL_HIP_RAGGED_SMALL_ROWS;
-        return t == SMALL ? small : nerrs >= EC_MAX_ROWS_PER_PASS || (last && !small);
+        const int small = isal_hip_uses_small_tile(nerrs);
+        return t == TILE_SMALL ? small : nerrs >= EC_MAX_ROWS_PER_PASS || (nerrs % EC_MAX_ROWS_PER_PASS && !small);
 }
 
 /* the pieces of one class in the blob, as byte offsets */
@@ -390,27 +393,21 @@ repair_upload_ragged(isal_hip_repair *r, const unsigned char *h_blob, size_t nbl
                      const uint32_t *h_tbl, size_t ntbl)
 {
         int c, t, e;
-        unsigned row;
         if (hipGetDevice(&r->device) != hipSuccess)
                 return ISAL_HIP_EHIP;
-        /* a row's shards are as long as that row */
+        /* a row's shards are as long as that row (no row here has length 0) */
         for (c = 0; c < r->nclass; c++) {
-                const size_t stride = (size_t) (r->k + r->cls[c].nerrs);
-                const uint64_t *hp = (const uint64_t *) (h_blob + offs[c * NPIECES + O_PTRS]);
-                const int *hl = (const int *) (h_blob + offs[c * NPIECES + O_LENS]);
-                for (row = 0; row < r->cls[c].nrows; row++)
-                        if ((e = isal_hip_batch_check_ptrs(hp + row * stride, stride, (size_t) hl[row], r->device)) !=
-                            ISAL_HIP_OK)
-                                return e;
+                const size_t *o = offs + c * NPIECES;
+                if ((e = isal_hip_obj_reach((const uint64_t *) (h_blob + o[O_PTRS]), r->cls[c].nrows,
+                                            (size_t) (r->k + r->cls[c].nerrs), 0, (const int *) (h_blob + o[O_LENS]),
+                                            r->device)) != ISAL_HIP_OK)
+                        return e;
         }
         if (!nblob)
                 return ISAL_HIP_OK;
-        if (hipMalloc((void **) &r->d_blob, nblob) != hipSuccess ||
-            hipMalloc((void **) &r->d_tbl, ntbl) != hipSuccess)
-                return ISAL_HIP_ENOMEM;
-        if (hipMemcpy(r->d_blob, h_blob, nblob, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(r->d_tbl, h_tbl, ntbl, hipMemcpyHostToDevice) != hipSuccess)
-                return ISAL_HIP_EHIP;
+        if ((e = isal_hip_obj_put(&r->d_blob, h_blob, nblob, 0)) != ISAL_HIP_OK ||
+            (e = isal_hip_obj_put(&r->d_tbl, h_tbl, ntbl, 0)) != ISAL_HIP_OK)
+                return e;
         for (c = 0; c < r->nclass; c++) {
                 rclass *cl = &r->cls[c];
                 const size_t *o = offs + c * NPIECES;
@@ -429,10 +426,8 @@ isal_hip_repair_create_ragged(isal_hip_repair **out, int k, int m, const unsigne
                               const int *lens, int max_errs, const unsigned char *nerrs, const unsigned char *errs,
                               unsigned char *const *shards, int *bad_stripe)
 {
-        static const int tile[NTILES] = { ISAL_HIP_RAGGED_TILE, ISAL_HIP_RAGGED_TILE_SMALL };
         isal_hip_repair *r = NULL;
         patset ps;
-        unsigned char mark[MAX_SHARDS];
         unsigned cnt[MAX_SHARDS + 1], base[MAX_SHARDS + 1]; /* rows of each count, their first row */
         int32_t *s_pat = NULL;                              /* -1: a stripe that lost nothing */
         uint32_t *first = NULL, *ord = NULL, *rstripe = NULL;
@@ -464,25 +459,11 @@ isal_hip_repair_create_ragged(isal_hip_repair **out, int k, int m, const unsigne
          * contract */
         memset(cnt, 0, sizeof(cnt));
         for (s = 0; s < nstripes && ret == ISAL_HIP_OK; s++) {
-                unsigned char *const *sh = shards + (size_t) s * m;
-                if (nerrs[s] > max_errs || lens[s] < 0)
-                        ret = ISAL_HIP_EINVAL;
-                else
-                        ret = mark_errs(m, nerrs[s], errs + (size_t) s * max_errs, mark);
-                for (i = 0; i < m && ret == ISAL_HIP_OK; i++)
-                        if (!sh[i] || ((uintptr_t) sh[i] & 15))
-                                ret = ISAL_HIP_EINVAL;
-                if (ret == ISAL_HIP_OK) {
-                        s_pat[s] = -1;
-                        if (nerrs[s] && (i = patset_find(&ps, nerrs[s], mark)) < 0)
-                                ret = i;
-                        else if (nerrs[s])
-                                s_pat[s] = i;
-                        if (ret == ISAL_HIP_OK && nerrs[s] && lens[s] > 0)
-                                cnt[nerrs[s]]++;
-                }
-                if (ret != ISAL_HIP_OK && ret != ISAL_HIP_ENOMEM && bad_stripe)
-                        *bad_stripe = (int) s;
+                s_pat[s] = -1;
+                ret = stripe_pattern(&ps, s, lens[s], nerrs[s], errs + (size_t) s * max_errs, shards + (size_t) s * m,
+                                     &s_pat[s], bad_stripe);
+                if (ret == ISAL_HIP_OK && nerrs[s] && lens[s] > 0)
+                        cnt[nerrs[s]]++;
         }
         if (ret != ISAL_HIP_OK)
                 goto done;
@@ -540,7 +521,7 @@ isal_hip_repair_create_ragged(isal_hip_repair **out, int k, int m, const unsigne
                 for (t = 0; t < NTILES; t++) {
                         if (!class_uses(c, t))
                                 continue;
-                        n = isal_hip_ragged_items((int) cl->nrows, cl_lens, tile[t], NULL);
+                        n = isal_hip_ragged_items((int) cl->nrows, cl_lens, isal_hip_tile_bytes(t), NULL);
                         if (n > (long long) ISAL_HIP_RAGGED_MAX_ITEMS) {
                                 ret = ISAL_HIP_EINVAL;
                                 goto done;
@@ -569,18 +550,13 @@ isal_hip_repair_create_ragged(isal_hip_repair **out, int k, int m, const unsigne
                 /* k survivors then the destinations in ascending order */
                 for (row = 0; row < cl->nrows; row++, hp += stride) {
                         const uint32_t st = rstripe[row0 + row];
-                        const int32_t p = s_pat[st];
-                        unsigned char *const *sh = shards + (size_t) st * m;
-                        for (i = 0; i < k; i++)
-                                hp[i] = (uint64_t) (uintptr_t) sh[ps.surv[(size_t) p * k + i]];
-                        for (i = 0; i < cl->nerrs; i++)
-                                hp[k + i] = (uint64_t) (uintptr_t) sh[ps.keys[(size_t) p * ps.kw + 1 + i]];
-                        h_pat[row] = ps.off[p];
+                        pattern_row(hp, &ps, s_pat[st], cl->nerrs, shards + (size_t) st * m);
+                        h_pat[row] = ps.off[s_pat[st]];
                 }
                 memcpy(h_blob + o[O_LENS], rlens + row0, (size_t) cl->nrows * sizeof(int));
                 for (t = 0; t < NTILES; t++)
                         if (cl->nitems[t])
-                                (void) isal_hip_ragged_items((int) cl->nrows, rlens + row0, tile[t],
+                                (void) isal_hip_ragged_items((int) cl->nrows, rlens + row0, isal_hip_tile_bytes(t),
                                                              (unsigned *) (h_blob + o[O_ITEMS + t]));
         }
         ret = repair_upload_ragged(r, h_blob, nblob, offs, ps.tbl, ps.tbl_dwords * 4);
@@ -608,8 +584,8 @@ repair_run_ragged(isal_hip_repair *r, void *stream)
         for (c = 0; c < r->nclass; c++) {
                 const rclass *cl = &r->cls[c];
                 if (isal_hip_launch_repair_ragged(cl->d_ptrs, r->k + cl->nerrs, cl->d_pat, r->d_tbl, cl->d_lens,
-                                                  cl->d_items[BIG], cl->nitems[BIG], cl->d_items[SMALL],
-                                                  cl->nitems[SMALL], r->k, cl->nerrs, stream))
+                                                  cl->d_items[TILE_BIG], cl->nitems[TILE_BIG], cl->d_items[TILE_SMALL],
+                                                  cl->nitems[TILE_SMALL], r->k, cl->nerrs, stream))
                         return ISAL_HIP_EHIP;
         }
         return ISAL_HIP_OK;
@@ -643,14 +619,10 @@ isal_hip_repair_destroy(isal_hip_repair *r)
 {
         if (!r)
                 return ISAL_HIP_OK;
-        if (r->d_ptrs)
-                (void) hipFree(r->d_ptrs);
-        if (r->d_pat)
-                (void) hipFree(r->d_pat);
-        if (r->d_tbl)
-                (void) hipFree(r->d_tbl);
-        if (r->d_blob)
-                (void) hipFree(r->d_blob);
+        isal_hip_obj_drop(r->d_ptrs);
+        isal_hip_obj_drop(r->d_pat);
+        isal_hip_obj_drop(r->d_tbl);
+        isal_hip_obj_drop(r->d_blob);
         free(r->cls);
         free(r);
         return ISAL_HIP_OK;

@@ -11,7 +11,8 @@
  * shard explains a syndrome.
  *
  * Host side, in this order (everything before the first HIP call is pure
- * arithmetic and returns the same codes on a host without a GPU):
+ * arithmetic and returns the same codes on a host without a GPU; the steps
+ * every stripe object shares are isal_hip_objects.c's):
  *   1. counts, then every shard pointer (non-NULL, 16-byte aligned) while the
  *      pointer table (per stripe k sources then rows parity rows) is written;
  *   2. the matrix is refused when two shards could explain one syndrome;
@@ -22,8 +23,9 @@
  * A scrub batch belongs to the device that was current when it was created
  * (ON_BATCH_DEVICE).
  *
- * The ragged scrub (isal_hip_scrub_create_ragged) is the same object where
- * every stripe has its own length: step 1 also takes each stripe's length,
+ * The ragged scrub (isal_hip_scrub_create_ragged) is the same object, built by
+ * the same create body (scrub_create), where every stripe has its own length:
+ * step 1 also takes each stripe's length,
  * the item count at the 4 KiB tile is checked against the launch limit before
  * step 2, and the upload also builds the work-item table of the ragged batch
  * (isal_hip_ragged_items). Its run is one ec_locate_rag launch over that table,
@@ -38,8 +40,6 @@
 #include "isal_hip.h"
 #include "isal_hip_internal.h"
 
-#define MAX_SHARDS 256 /* shard indices are bytes */
-
 struct isal_hip_scrub {
         int len, k, rows, nstripes, device;
         uint64_t *d_ptrs;
@@ -52,10 +52,6 @@ struct isal_hip_scrub {
         int *d_lens;
         unsigned *d_items;
 };
-
-/* tests/sanitize/scrub_host.c links this file without the ragged pieces */
-#pragma weak isal_hip_ragged_items
-#pragma weak isal_hip_launch_locate_ragged
 
 /* C[l][j] for j < k, the identity's column j - k beyond */
 static unsigned char
@@ -174,59 +170,36 @@ static int
 scrub_upload(isal_hip_scrub *s, const uint64_t *h_ptrs, const uint32_t *h_tbl, const unsigned char *h_loc,
              const int *lens)
 {
-        unsigned *h_items;
-        const size_t stride = (size_t) (s->k + s->rows);
-        const size_t nptr = (size_t) s->nstripes * stride;
+        const size_t stride = (size_t) (s->k + s->rows), nstripes = (size_t) s->nstripes;
         const size_t ntbl = isal_hip_tables_dwords(s->k, s->rows) * 4;
-        const size_t nloc = (size_t) (s->rows + 2) * (size_t) s->k;
-        int i, e;
+        int e;
         if (hipGetDevice(&s->device) != hipSuccess)
                 return ISAL_HIP_EHIP;
-        if (!lens && s->len > 0 &&
-            (e = isal_hip_batch_check_ptrs(h_ptrs, nptr, (size_t) s->len, s->device)) != ISAL_HIP_OK)
+        if ((e = isal_hip_obj_reach(h_ptrs, nstripes, stride, (size_t) s->len, lens, s->device)) != ISAL_HIP_OK ||
+            (e = isal_hip_obj_put(&s->d_ptrs, h_ptrs, nstripes * stride * 8, 0)) != ISAL_HIP_OK ||
+            (e = isal_hip_obj_put(&s->d_tbl, h_tbl, ntbl, 4)) != ISAL_HIP_OK ||
+            (e = isal_hip_obj_put(&s->d_loc, h_loc, (size_t) (s->rows + 2) * (size_t) s->k, 0)) != ISAL_HIP_OK)
                 return e;
-        /* a ragged stripe's shards are as long as that stripe */
-        for (i = 0; lens && i < s->nstripes; i++)
-                if (lens[i] > 0 && (e = isal_hip_batch_check_ptrs(h_ptrs + (size_t) i * stride, stride,
-                                                                  (size_t) lens[i], s->device)) != ISAL_HIP_OK)
-                        return e;
-        if (hipMalloc((void **) &s->d_ptrs, nptr * 8) != hipSuccess ||
-            hipMalloc((void **) &s->d_tbl, ntbl + 4) != hipSuccess ||
-            hipMalloc((void **) &s->d_loc, nloc) != hipSuccess)
-                return ISAL_HIP_ENOMEM;
-        if (hipMemcpy(s->d_ptrs, h_ptrs, nptr * 8, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(s->d_tbl, h_tbl, ntbl, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(s->d_loc, h_loc, nloc, hipMemcpyHostToDevice) != hipSuccess)
-                return ISAL_HIP_EHIP;
         if (!lens)
                 return ISAL_HIP_OK;
-        if (hipMalloc((void **) &s->d_lens, (size_t) s->nstripes * sizeof(int)) != hipSuccess)
-                return ISAL_HIP_ENOMEM;
-        if (hipMemcpy(s->d_lens, lens, (size_t) s->nstripes * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
-                return ISAL_HIP_EHIP;
-        if (!s->nitems)
-                return ISAL_HIP_OK;
-        h_items = (unsigned *) malloc((size_t) s->nitems * 8);
-        if (!h_items || hipMalloc((void **) &s->d_items, (size_t) s->nitems * 8) != hipSuccess) {
-                free(h_items);
-                return ISAL_HIP_ENOMEM;
-        }
-        (void) isal_hip_ragged_items(s->nstripes, lens, ISAL_HIP_RAGGED_TILE, h_items);
-        e = hipMemcpy(s->d_items, h_items, (size_t) s->nitems * 8, hipMemcpyHostToDevice) != hipSuccess;
-        free(h_items);
-        return e ? ISAL_HIP_EHIP : ISAL_HIP_OK;
+        if ((e = isal_hip_obj_put(&s->d_lens, lens, nstripes * sizeof(int), 0)) != ISAL_HIP_OK)
+                return e;
+        return isal_hip_obj_put_items(&s->d_items, s->nstripes, lens, ISAL_HIP_RAGGED_TILE, s->nitems);
 }
 
-int
-isal_hip_scrub_create(isal_hip_scrub **out, int len, int k, int rows, const unsigned char *gftbls, int nstripes,
-                      unsigned char *const *data, unsigned char *const *coding, int *bad_stripe)
+/* Both kinds of object: the uniform one of len (lens == NULL) and the ragged
+ * one, which must have its lens. */
+static int
+scrub_create(isal_hip_scrub **out, int ragged, int len, const int *lens, int k, int rows,
+             const unsigned char *gftbls, int nstripes, unsigned char *const *data, unsigned char *const *coding,
+             int *bad_stripe)
 {
         isal_hip_scrub *sc = NULL;
         uint64_t *h_ptrs = NULL;
         uint32_t *h_tbl = NULL;
         unsigned char *h_loc = NULL;
-        long long s;
-        int i, ret = ISAL_HIP_OK;
+        long long s, n = 0;
+        int ret = ISAL_HIP_OK;
         size_t stride;
 
         if (bad_stripe)
@@ -237,80 +210,7 @@ isal_hip_scrub_create(isal_hip_scrub **out, int len, int k, int rows, const unsi
         /* one row cannot tell shards apart; a syndrome must be whole inside
          * one pass of the kernel */
         if (len < 0 || k < 1 || rows < 2 || rows > EC_MAX_ROWS_PER_PASS || k + rows > MAX_SHARDS || !gftbls ||
-            nstripes < 1 || !data || !coding)
-                return ISAL_HIP_EINVAL;
-        stride = (size_t) k + (size_t) rows;
-
-        h_ptrs = (uint64_t *) malloc((size_t) nstripes * stride * 8);
-        if (!h_ptrs)
-                return ISAL_HIP_ENOMEM;
-        /* 1: every stripe's pointers while its table row is written */
-        for (s = 0; s < nstripes && ret == ISAL_HIP_OK; s++) {
-                uint64_t *hp = h_ptrs + (size_t) s * stride;
-                for (i = 0; i < k; i++)
-                        hp[i] = (uint64_t) (uintptr_t) data[(size_t) s * k + i];
-                for (i = 0; i < rows; i++)
-                        hp[k + i] = (uint64_t) (uintptr_t) coding[(size_t) s * rows + i];
-                for (i = 0; i < (int) stride; i++)
-                        if (!hp[i] || (hp[i] & 15))
-                                ret = ISAL_HIP_EINVAL;
-                if (ret != ISAL_HIP_OK && bad_stripe)
-                        *bad_stripe = (int) s;
-        }
-        /* 2: two shards that explain the same syndrome cannot be told apart */
-        if (ret == ISAL_HIP_OK)
-                ret = isal_hip_scrub_ambiguity(k, rows, gftbls, NULL);
-        if (ret != ISAL_HIP_OK)
-                goto done;
-
-        /* 3: the encode's tables and masks, the mismatch branch's tables */
-        h_tbl = (uint32_t *) malloc(isal_hip_tables_dwords(k, rows) * 4 + 4);
-        h_loc = (unsigned char *) malloc((size_t) (rows + 2) * (size_t) k);
-        sc = (isal_hip_scrub *) calloc(1, sizeof(*sc));
-        if (!h_tbl || !h_loc || !sc) {
-                ret = ISAL_HIP_ENOMEM;
-                goto done;
-        }
-        isal_hip_build_tables(k, rows, gftbls, h_tbl);
-        build_loc(k, rows, gftbls, h_loc);
-        isal_hip_enc_masks(k, rows, gftbls, &sc->em);
-        sc->len = len;
-        sc->k = k;
-        sc->rows = rows;
-        sc->nstripes = nstripes;
-        ret = scrub_upload(sc, h_ptrs, h_tbl, h_loc, NULL);
-done:
-        free(h_ptrs);
-        free(h_tbl);
-        free(h_loc);
-        if (ret != ISAL_HIP_OK) {
-                isal_hip_scrub_destroy(sc);
-                return ret;
-        }
-        *out = sc;
-        return ISAL_HIP_OK;
-}
-
-int
-isal_hip_scrub_create_ragged(isal_hip_scrub **out, int k, int rows, const unsigned char *gftbls, int nstripes,
-                             const int *lens, unsigned char *const *data, unsigned char *const *coding,
-                             int *bad_stripe)
-{
-        isal_hip_scrub *sc = NULL;
-        uint64_t *h_ptrs = NULL;
-        uint32_t *h_tbl = NULL;
-        unsigned char *h_loc = NULL;
-        long long s, n = 0;
-        int i, ret = ISAL_HIP_OK;
-        size_t stride;
-
-        if (bad_stripe)
-                *bad_stripe = -1;
-        if (!out)
-                return ISAL_HIP_EINVAL;
-        *out = NULL;
-        if (k < 1 || rows < 2 || rows > EC_MAX_ROWS_PER_PASS || k + rows > MAX_SHARDS || !gftbls || nstripes < 1 ||
-            !lens || !data || !coding)
+            nstripes < 1 || (ragged && !lens) || !data || !coding)
                 return ISAL_HIP_EINVAL;
         stride = (size_t) k + (size_t) rows;
 
@@ -320,20 +220,15 @@ isal_hip_scrub_create_ragged(isal_hip_scrub **out, int k, int rows, const unsign
         /* 1: every stripe's length and pointers while its table row is written */
         for (s = 0; s < nstripes && ret == ISAL_HIP_OK; s++) {
                 uint64_t *hp = h_ptrs + (size_t) s * stride;
-                for (i = 0; i < k; i++)
-                        hp[i] = (uint64_t) (uintptr_t) data[(size_t) s * k + i];
-                for (i = 0; i < rows; i++)
-                        hp[k + i] = (uint64_t) (uintptr_t) coding[(size_t) s * rows + i];
-                if (lens[s] < 0)
+                if (isal_hip_obj_ptr_row(hp, data + (size_t) s * k, (size_t) k) != ISAL_HIP_OK ||
+                    isal_hip_obj_ptr_row(hp + k, coding + (size_t) s * rows, (size_t) rows) != ISAL_HIP_OK ||
+                    (lens && lens[s] < 0))
                         ret = ISAL_HIP_EINVAL;
-                for (i = 0; i < (int) stride; i++)
-                        if (!hp[i] || (hp[i] & 15))
-                                ret = ISAL_HIP_EINVAL;
                 if (ret != ISAL_HIP_OK && bad_stripe)
                         *bad_stripe = (int) s;
         }
         /* one launch covers every item (the only tile size here is 4 KiB) */
-        if (ret == ISAL_HIP_OK &&
+        if (ret == ISAL_HIP_OK && lens &&
             (n = isal_hip_ragged_items(nstripes, lens, ISAL_HIP_RAGGED_TILE, NULL)) > (long long) ISAL_HIP_RAGGED_MAX_ITEMS)
                 ret = ISAL_HIP_EINVAL;
         /* 2: two shards that explain the same syndrome cannot be told apart */
@@ -342,8 +237,8 @@ isal_hip_scrub_create_ragged(isal_hip_scrub **out, int k, int rows, const unsign
         if (ret != ISAL_HIP_OK)
                 goto done;
 
-        /* 3: the encode's tables, the mismatch branch's tables; the item table
-         * at the upload */
+        /* 3: the encode's tables, the mismatch branch's tables; the uniform
+         * kind's masks, the ragged kind's item table at the upload */
         h_tbl = (uint32_t *) malloc(isal_hip_tables_dwords(k, rows) * 4 + 4);
         h_loc = (unsigned char *) malloc((size_t) (rows + 2) * (size_t) k);
         sc = (isal_hip_scrub *) calloc(1, sizeof(*sc));
@@ -353,8 +248,11 @@ isal_hip_scrub_create_ragged(isal_hip_scrub **out, int k, int rows, const unsign
         }
         isal_hip_build_tables(k, rows, gftbls, h_tbl);
         build_loc(k, rows, gftbls, h_loc);
-        sc->ragged = 1;
+        if (!lens)
+                isal_hip_enc_masks(k, rows, gftbls, &sc->em);
+        sc->ragged = lens != NULL;
         sc->nitems = (unsigned) n;
+        sc->len = len;
         sc->k = k;
         sc->rows = rows;
         sc->nstripes = nstripes;
@@ -369,6 +267,21 @@ done:
         }
         *out = sc;
         return ISAL_HIP_OK;
+}
+
+int
+isal_hip_scrub_create(isal_hip_scrub **out, int len, int k, int rows, const unsigned char *gftbls, int nstripes,
+                      unsigned char *const *data, unsigned char *const *coding, int *bad_stripe)
+{
+        return scrub_create(out, 0, len, NULL, k, rows, gftbls, nstripes, data, coding, bad_stripe);
+}
+
+int
+isal_hip_scrub_create_ragged(isal_hip_scrub **out, int k, int rows, const unsigned char *gftbls, int nstripes,
+                             const int *lens, unsigned char *const *data, unsigned char *const *coding,
+                             int *bad_stripe)
+{
+        return scrub_create(out, 1, 0, lens, k, rows, gftbls, nstripes, data, coding, bad_stripe);
 }
 
 static int
@@ -398,16 +311,11 @@ isal_hip_scrub_destroy(isal_hip_scrub *s)
 {
         if (!s)
                 return ISAL_HIP_OK;
-        if (s->d_ptrs)
-                (void) hipFree(s->d_ptrs);
-        if (s->d_tbl)
-                (void) hipFree(s->d_tbl);
-        if (s->d_loc)
-                (void) hipFree(s->d_loc);
-        if (s->d_lens)
-                (void) hipFree(s->d_lens);
-        if (s->d_items)
-                (void) hipFree(s->d_items);
+        isal_hip_obj_drop(s->d_ptrs);
+        isal_hip_obj_drop(s->d_tbl);
+        isal_hip_obj_drop(s->d_loc);
+        isal_hip_obj_drop(s->d_lens);
+        isal_hip_obj_drop(s->d_items);
         free(s);
         return ISAL_HIP_OK;
 }

@@ -1,0 +1,155 @@
+/*
+ * hip_stubs.c — TEST INFRASTRUCTURE: the HIP runtime, the engine's device
+ * switch and its reachability check as the *_host.c programs see them, the
+ * helpers of their drivers, and a default for every kernel launcher the
+ * stripe objects' host sources reference. A program defines the launchers it
+ * drives; the weak ones here only fail.
+ */
+#include "hip_stubs.h"
+
+int g_hip_calls, g_allocs, g_checks;
+size_t g_check_len[64];
+static volatile unsigned char g_sink;
+
+hipError_t
+hipGetDevice(int *d)
+{
+        g_hip_calls++;
+        *d = 0;
+        return hipSuccess;
+}
+
+hipError_t
+hipMalloc(void **p, size_t n)
+{
+        g_hip_calls++;
+        CHECK(n > 0);
+        *p = malloc(n); /* exactly n: ASan guards the end of every table */
+        g_allocs++;
+        return *p ? hipSuccess : hipErrorOutOfMemory;
+}
+
+hipError_t
+hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind kind)
+{
+        (void) kind;
+        g_hip_calls++;
+        memcpy(d, s, n);
+        return hipSuccess;
+}
+
+hipError_t
+hipFree(void *p)
+{
+        free(p);
+        g_allocs--;
+        return hipSuccess;
+}
+
+int
+isal_hip_dev_enter(int dev)
+{
+        (void) dev;
+        return -1;
+}
+
+void
+isal_hip_dev_leave(int prev)
+{
+        (void) prev;
+}
+
+/* Never over no bytes (zero-length stripes are not classified), and over the
+ * length the shards have: the last byte of each is touched. */
+int
+isal_hip_batch_check_ptrs(const uint64_t *ptrs, size_t n, size_t len, int dev)
+{
+        size_t i;
+        (void) dev;
+        g_hip_calls++;
+        CHECK(len > 0);
+        if (g_checks < 64)
+                g_check_len[g_checks] = len;
+        g_checks++;
+        for (i = 0; i < n; i++) {
+                if (!ptrs[i])
+                        return ISAL_HIP_EINVAL;
+                g_sink = ((const unsigned char *) (uintptr_t) ptrs[i])[len - 1];
+        }
+        return ISAL_HIP_OK;
+}
+
+/* ---- the drivers' helpers ------------------------------------------------- */
+
+static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
+
+unsigned
+rnd(unsigned n)
+{
+        rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
+        return (unsigned) (rng_state >> 33) % n;
+}
+
+unsigned char *
+shard(int len)
+{
+        unsigned char *p;
+        CHECK(posix_memalign((void **) &p, 16, (size_t) (len ? len : 1)) == 0);
+        return p;
+}
+
+unsigned char
+coef_of(const uint32_t *tbl, int k, int rows, int l, int j)
+{
+        const int r0 = l / EC_MAX_ROWS_PER_PASS * EC_MAX_ROWS_PER_PASS;
+        const int P = rows - r0 < EC_MAX_ROWS_PER_PASS ? rows - r0 : EC_MAX_ROWS_PER_PASS;
+        const uint32_t *t = tbl + (size_t) EC_TBL_DWORDS * k * r0 + ((size_t) j * P + (l - r0)) * EC_TBL_DWORDS;
+        return (unsigned char) (t[0] >> 8); /* entry 1 of c * {0..7} */
+}
+
+/* ---- the launchers a program does not drive -------------------------------- */
+
+#define NOT_DRIVEN                                        \
+        {                                                 \
+                CHECK(!"not driven by this program");     \
+                return 1;                                 \
+        }
+
+__attribute__((weak)) int
+isal_hip_launch_repair(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_pat, const uint32_t *d_tbl,
+                       unsigned tbl_stride, int len, int k, int rows, long long nrows, void *stream) NOT_DRIVEN
+
+__attribute__((weak)) int
+isal_hip_launch_repair_ragged(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_pat, const uint32_t *d_tbl,
+                              const int *d_lens, const unsigned *d_items, unsigned nitems,
+                              const unsigned *d_items_small, unsigned nitems_small, int k, int rows,
+                              void *stream) NOT_DRIVEN
+
+__attribute__((weak)) int
+isal_hip_launch_overwrite(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_idx, const uint32_t *d_tbl,
+                          int len, int k, int rows, int nw, long long nstripes, int commit, void *stream) NOT_DRIVEN
+
+__attribute__((weak)) int
+isal_hip_launch_overwrite_ragged(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_idx,
+                                 const uint32_t *d_tbl, const int *d_lens, const int *d_nw, const unsigned *d_items,
+                                 unsigned nitems, int k, int rows, int max_nw, int commit, void *stream) NOT_DRIVEN
+
+__attribute__((weak)) int
+isal_hip_launch_locate_batch(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_tbl, int len, int k,
+                             int rows, long long nstripes, const isal_hip_encmask *em, const unsigned char *d_loc,
+                             unsigned *verdict, void *stream) NOT_DRIVEN
+
+__attribute__((weak)) int
+isal_hip_launch_locate_ragged(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_tbl, const int *d_lens,
+                              const unsigned *d_items, unsigned nitems, int k, int rows, long long nstripes,
+                              const unsigned char *d_loc, unsigned *verdict, void *stream) NOT_DRIVEN
+
+__attribute__((weak)) int
+isal_hip_launch_encode_ragged(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_tbl, const int *d_lens,
+                              const unsigned *d_items, unsigned nitems, const unsigned *d_items_small,
+                              unsigned nitems_small, int k, int rows, void *stream) NOT_DRIVEN
+
+__attribute__((weak)) int
+isal_hip_launch_verify_ragged(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_tbl, const int *d_lens,
+                              const unsigned *d_items, unsigned nitems, int k, int rows, long long nstripes,
+                              unsigned long long *bad, void *stream) NOT_DRIVEN

@@ -5,7 +5,7 @@
  * the tables at stride max_nw with zeroed padding, the lengths, the counts and
  * the item table) under ASan + UBSan, as a stand-alone program.
  *
- * The HIP runtime and the kernel launchers are replaced by the stubs below
+ * The HIP runtime (hip_stubs.c) and the kernel launchers (below) are stubs
  * ("device" memory is host memory), so the program needs no GPU and what
  * create() uploads can be read back: the launch stub applies every item's
  * delta on the CPU from the pointer, index, length, count, item and
@@ -15,136 +15,18 @@
  * reaches past a stripe's own length, or a padded slot that is dereferenced,
  * is an ASan report.
  *
- * Build and run by hand, from the repository root:
- *   gcc -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=all \
- *       -D__HIP_PLATFORM_AMD__=1 -Iinclude -Iisa-l_amd/csrc -I/opt/rocm/include \
- *       tests/sanitize/overwrite_ragged_host.c isa-l_amd/csrc/isal_hip_overwrite.c \
- *       isa-l_amd/csrc/isal_hip_ragged.c isa-l_amd/csrc/gf_host.c isa-l_amd/csrc/isal_hip_knobs.c \
- *       -lpthread -o isa-l_amd/build/asan/overwrite_ragged_host
- *   isa-l_amd/build/asan/overwrite_ragged_host
+ * Built by this directory's Makefile (make -C tests/sanitize) and run by
+ * tests/test_sanitizers_cpu.py; the stubs every such program shares are in
+ * hip_stubs.c.
  */
-#include <hip/hip_runtime_api.h>
 #include <limits.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
-#include "erasure_code.h"
-#include "isal_hip.h"
-#include "isal_hip_internal.h"
+#include "hip_stubs.h"
 
-#define CHECK(c)                                                                 \
-        do {                                                                     \
-                if (!(c)) {                                                      \
-                        fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); \
-                        exit(1);                                                 \
-                }                                                                \
-        } while (0)
+/* ---- stubs: the launchers this program drives ------------------------------ */
 
-/* ---- stubs: the HIP runtime and the engine's launchers -------------------- */
-
-static int g_launches, g_commits, g_allocs;
+static int g_launches, g_commits;
 static unsigned g_items;
-static volatile unsigned char g_sink;
-
-hipError_t
-hipGetDevice(int *d)
-{
-        *d = 0;
-        return hipSuccess;
-}
-
-hipError_t
-hipMalloc(void **p, size_t n)
-{
-        CHECK(n > 0);
-        *p = malloc(n);
-        g_allocs++;
-        return *p ? hipSuccess : hipErrorOutOfMemory;
-}
-
-hipError_t
-hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind kind)
-{
-        (void) kind;
-        memcpy(d, s, n);
-        return hipSuccess;
-}
-
-hipError_t
-hipFree(void *p)
-{
-        free(p);
-        g_allocs--;
-        return hipSuccess;
-}
-
-int
-isal_hip_dev_enter(int dev)
-{
-        (void) dev;
-        return -1;
-}
-
-void
-isal_hip_dev_leave(int prev)
-{
-        (void) prev;
-}
-
-/* the reachability check runs with the stripe's own length over its live
- * pointers only: touch the last byte of each */
-int
-isal_hip_batch_check_ptrs(const uint64_t *ptrs, size_t n, size_t len, int dev)
-{
-        size_t i;
-        (void) dev;
-        CHECK(len > 0);
-        for (i = 0; i < n; i++) {
-                if (!ptrs[i])
-                        return ISAL_HIP_EINVAL;
-                g_sink = ((const unsigned char *) (uintptr_t) ptrs[i])[len - 1];
-        }
-        return ISAL_HIP_OK;
-}
-
-/* isal_hip_ragged.c and the uniform create are linked but not driven here */
-int
-isal_hip_launch_encode_ragged(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_tbl, const int *d_lens,
-                              const unsigned *d_items, unsigned nitems, const unsigned *d_items_small,
-                              unsigned nitems_small, int k, int rows, void *stream)
-{
-        CHECK(!"not driven by this program");
-        return 1;
-}
-
-int
-isal_hip_launch_verify_ragged(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_tbl, const int *d_lens,
-                              const unsigned *d_items, unsigned nitems, int k, int rows, long long nstripes,
-                              unsigned long long *bad, void *stream)
-{
-        CHECK(!"not driven by this program");
-        return 1;
-}
-
-int
-isal_hip_launch_overwrite(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_idx, const uint32_t *d_tbl,
-                          int len, int k, int rows, int nw, long long nstripes, int commit, void *stream)
-{
-        CHECK(!"not driven by this program");
-        return 1;
-}
-
-/* coefficient (row l, source j) of the table image */
-static unsigned char
-coef_of(const uint32_t *tbl, int k, int rows, int l, int j)
-{
-        const int r0 = l / EC_MAX_ROWS_PER_PASS * EC_MAX_ROWS_PER_PASS;
-        const int P = rows - r0 < EC_MAX_ROWS_PER_PASS ? rows - r0 : EC_MAX_ROWS_PER_PASS;
-        const uint32_t *t = tbl + (size_t) EC_TBL_DWORDS * k * r0 + ((size_t) j * P + (l - r0)) * EC_TBL_DWORDS;
-        return (unsigned char) (t[0] >> 8); /* entry 1 of c * {0..7} */
-}
 
 /* Every item folds its 2 KiB tile of its stripe's live slots into every row,
  * bounded by the stripe's own length; commit then stores new over old. */
@@ -197,24 +79,6 @@ isal_hip_launch_overwrite_ragged(const uint64_t *d_ptrs, int ptr_stride, const u
 }
 
 /* ---- the driver ----------------------------------------------------------- */
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-
-static unsigned
-rnd(unsigned n)
-{
-        rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
-        return (unsigned) (rng_state >> 33) % n;
-}
-
-/* exactly len bytes (one byte at len 0, never touched), 16-byte aligned */
-static unsigned char *
-shard(int len)
-{
-        unsigned char *p;
-        CHECK(posix_memalign((void **) &p, 16, (size_t) (len ? len : 1)) == 0);
-        return p;
-}
 
 /* parity[l] of data[0..k) for the m x k matrix a, into out[l] */
 static void

@@ -4,7 +4,7 @@
  * the pointer, coefficient, length and item tables) under ASan + UBSan, as a
  * stand-alone program.
  *
- * The HIP runtime and the kernel launchers are replaced by the stubs below
+ * The HIP runtime (hip_stubs.c) and the kernel launchers (below) are stubs
  * ("device" memory is host memory), so the program needs no GPU and the
  * tables create() uploads can be read back: the launch stubs walk the
  * uploaded item table of each pass, take every item's length from the
@@ -15,93 +15,15 @@
  * exactly its stripe's length, so a byte past any stripe's own length is an
  * ASan report.
  *
- * Build and run by hand, from the repository root:
- *   gcc -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=all \
- *       -D__HIP_PLATFORM_AMD__=1 -Iinclude -Iisa-l_amd/csrc -I/opt/rocm/include \
- *       tests/sanitize/ragged_host.c isa-l_amd/csrc/isal_hip_ragged.c isa-l_amd/csrc/gf_host.c \
- *       isa-l_amd/csrc/ec_cpu.c isa-l_amd/csrc/isal_hip_knobs.c -lpthread -o isa-l_amd/build/asan/ragged_host
- *   isa-l_amd/build/asan/ragged_host
+ * Built by this directory's Makefile (make -C tests/sanitize) and run by
+ * tests/test_sanitizers_cpu.py; the stubs every such program shares are in
+ * hip_stubs.c.
  */
-#include <hip/hip_runtime_api.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+#include "hip_stubs.h"
 
-#include "erasure_code.h"
-#include "isal_hip.h"
-#include "isal_hip_internal.h"
+/* ---- stubs: the launchers this program drives ------------------------------ */
 
-#define CHECK(c)                                                                 \
-        do {                                                                     \
-                if (!(c)) {                                                      \
-                        fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); \
-                        exit(1);                                                 \
-                }                                                                \
-        } while (0)
-
-/* ---- stubs: the HIP runtime and the engine's launchers -------------------- */
-
-static int g_launches, g_hip_calls;
-
-hipError_t
-hipGetDevice(int *d)
-{
-        g_hip_calls++;
-        *d = 0;
-        return hipSuccess;
-}
-
-hipError_t
-hipMalloc(void **p, size_t n)
-{
-        g_hip_calls++;
-        CHECK(n > 0);
-        *p = malloc(n); /* exactly n: ASan guards the end of every table */
-        return *p ? hipSuccess : hipErrorOutOfMemory;
-}
-
-hipError_t
-hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind kind)
-{
-        (void) kind;
-        g_hip_calls++;
-        memcpy(d, s, n);
-        return hipSuccess;
-}
-
-hipError_t
-hipFree(void *p)
-{
-        free(p);
-        return hipSuccess;
-}
-
-int
-isal_hip_dev_enter(int dev)
-{
-        (void) dev;
-        return -1;
-}
-
-void
-isal_hip_dev_leave(int prev)
-{
-        (void) prev;
-}
-
-int
-isal_hip_batch_check_ptrs(const uint64_t *ptrs, size_t n, size_t len, int dev)
-{
-        size_t i;
-        (void) dev;
-        g_hip_calls++;
-        CHECK(len > 0); /* zero-length stripes are not classified */
-        for (i = 0; i < n; i++)
-                if (!ptrs[i])
-                        return ISAL_HIP_EINVAL;
-        return ISAL_HIP_OK;
-}
+static int g_launches;
 
 /* ec_encode_data_base as the library serves it for host shards without a GPU:
  * the engine's CPU route (ec_cpu.c), none of the code under test */
@@ -109,17 +31,6 @@ void
 ec_encode_data_base(int len, int k, int rows, unsigned char *gftbls, unsigned char **data, unsigned char **coding)
 {
         (void) isal_cpu_run(ISAL_HIP_OP_ENCODE, 0, len, k, rows, 0, gftbls, data, k, coding);
-}
-
-/* coefficient (row r of all rows, source j) of the device table image: pass
- * g = r / 8 starts at dword 5 * k * 8g and is laid out [j][l < P][5] */
-static unsigned char
-coef_of(const uint32_t *tbl, int k, int rows, int r, int j)
-{
-        const int r0 = r / EC_MAX_ROWS_PER_PASS * EC_MAX_ROWS_PER_PASS;
-        const int P = rows - r0 < EC_MAX_ROWS_PER_PASS ? rows - r0 : EC_MAX_ROWS_PER_PASS;
-        const uint32_t *t = tbl + (size_t) EC_TBL_DWORDS * k * r0 + ((size_t) j * P + (r - r0)) * EC_TBL_DWORDS;
-        return (unsigned char) (t[0] >> 8); /* entry 1 of c * {0..7} */
 }
 
 /* one item: bytes [tile * span, min(len, (tile + 1) * span)) of rows [r0, r0 + P) */
@@ -220,24 +131,6 @@ isal_hip_launch_verify_ragged(const uint64_t *d_ptrs, int ptr_stride, const uint
 }
 
 /* ---- the driver ----------------------------------------------------------- */
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-
-static unsigned
-rnd(unsigned n)
-{
-        rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
-        return (unsigned) (rng_state >> 33) % n;
-}
-
-static unsigned char *
-shard(int len)
-{
-        unsigned char *p;
-        /* a multiple of 16 would hide an overrun of up to 15 bytes: ask for len */
-        CHECK(posix_memalign((void **) &p, 16, (size_t) (len ? len : 1)) == 0);
-        return p;
-}
 
 static void
 run_geometry(int cauchy, int k, int rows, int nstripes, const int *lens)

@@ -3,104 +3,21 @@
  * (isa-l_amd/csrc/isal_hip_repair.c: isal_hip_decode_matrix, the pattern
  * dedupe, the sort by pattern) under ASan + UBSan, as a stand-alone program.
  *
- * The HIP runtime and the kernel launcher are replaced by the stubs below
+ * The HIP runtime (hip_stubs.c) and the kernel launcher (below) are stubs
  * ("device" memory is host memory), so the program needs no GPU and the
  * tables create() uploads can be read back: the launch stub rebuilds every
  * stripe on the CPU from the pointer table, the pattern indices and the
  * coefficient tables it is handed, and compares with the encoded shards.
  *
- * Build and run by hand, from the repository root:
- *   gcc -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=all \
- *       -D__HIP_PLATFORM_AMD__=1 -Iinclude -Iisa-l_amd/csrc -I/opt/rocm/include \
- *       tests/sanitize/repair_host.c isa-l_amd/csrc/isal_hip_repair.c isa-l_amd/csrc/gf_host.c \
- *       isa-l_amd/csrc/isal_hip_knobs.c -lpthread -o isa-l_amd/build/asan/repair_host
- *   isa-l_amd/build/asan/repair_host
+ * Built by this directory's Makefile (make -C tests/sanitize) and run by
+ * tests/test_sanitizers_cpu.py; the stubs every such program shares are in
+ * hip_stubs.c.
  */
-#include <hip/hip_runtime_api.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+#include "hip_stubs.h"
 
-#include "erasure_code.h"
-#include "isal_hip.h"
-#include "isal_hip_internal.h"
-
-#define CHECK(c)                                                                 \
-        do {                                                                     \
-                if (!(c)) {                                                      \
-                        fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); \
-                        exit(1);                                                 \
-                }                                                                \
-        } while (0)
-
-/* ---- stubs: the HIP runtime and the engine's launcher --------------------- */
+/* ---- stubs: the launchers this program drives ------------------------------ */
 
 static int g_launches, g_rows_checked, g_unsorted;
-
-hipError_t
-hipGetDevice(int *d)
-{
-        *d = 0;
-        return hipSuccess;
-}
-
-hipError_t
-hipMalloc(void **p, size_t n)
-{
-        *p = malloc(n ? n : 1);
-        return *p ? hipSuccess : hipErrorOutOfMemory;
-}
-
-hipError_t
-hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind kind)
-{
-        (void) kind;
-        memcpy(d, s, n);
-        return hipSuccess;
-}
-
-hipError_t
-hipFree(void *p)
-{
-        free(p);
-        return hipSuccess;
-}
-
-int
-isal_hip_dev_enter(int dev)
-{
-        (void) dev;
-        return -1;
-}
-
-void
-isal_hip_dev_leave(int prev)
-{
-        (void) prev;
-}
-
-int
-isal_hip_batch_check_ptrs(const uint64_t *ptrs, size_t n, size_t len, int dev)
-{
-        size_t i;
-        (void) len;
-        (void) dev;
-        for (i = 0; i < n; i++)
-                if (!ptrs[i])
-                        return ISAL_HIP_EINVAL;
-        return ISAL_HIP_OK;
-}
-
-/* coefficient (row l, source j) of one pattern's table image */
-static unsigned char
-coef_of(const uint32_t *tbl, int k, int rows, int l, int j)
-{
-        const int r0 = l / EC_MAX_ROWS_PER_PASS * EC_MAX_ROWS_PER_PASS;
-        const int P = rows - r0 < EC_MAX_ROWS_PER_PASS ? rows - r0 : EC_MAX_ROWS_PER_PASS;
-        const uint32_t *t = tbl + (size_t) EC_TBL_DWORDS * k * r0 + ((size_t) j * P + (l - r0)) * EC_TBL_DWORDS;
-        return (unsigned char) (t[0] >> 8); /* entry 1 of c * {0..7} */
-}
 
 int
 isal_hip_launch_repair(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_pat, const uint32_t *d_tbl,
@@ -131,15 +48,6 @@ isal_hip_launch_repair(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d
 }
 
 /* ---- the driver ----------------------------------------------------------- */
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-
-static unsigned
-rnd(unsigned n)
-{
-        rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
-        return (unsigned) (rng_state >> 33) % n;
-}
 
 /* nerrs distinct indices below m, in a random order */
 static void

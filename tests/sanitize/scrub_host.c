@@ -4,7 +4,7 @@
  * isal_hip_locate_syndrome, create's refusals, the pointer, coefficient and
  * location tables) under ASan + UBSan, as a stand-alone program.
  *
- * The HIP runtime and the kernel launcher are replaced by the stubs below
+ * The HIP runtime (hip_stubs.c) and the kernel launcher (below) are stubs
  * ("device" memory is host memory), so the program needs no GPU and the
  * tables create() uploads can be read back: the launch stub walks every byte
  * column of every stripe from the pointer table and names the shard from the
@@ -12,95 +12,15 @@
  * mismatch branch does; the driver compares the verdicts with the corruption
  * it planted and with isal_hip_locate_syndrome.
  *
- * Build and run by hand, from the repository root:
- *   gcc -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=all \
- *       -D__HIP_PLATFORM_AMD__=1 -Iinclude -Iisa-l_amd/csrc -I/opt/rocm/include \
- *       tests/sanitize/scrub_host.c isa-l_amd/csrc/isal_hip_scrub.c isa-l_amd/csrc/gf_host.c \
- *       isa-l_amd/csrc/isal_hip_knobs.c -lpthread -o isa-l_amd/build/asan/scrub_host
- *   isa-l_amd/build/asan/scrub_host
+ * Built by this directory's Makefile (make -C tests/sanitize) and run by
+ * tests/test_sanitizers_cpu.py; the stubs every such program shares are in
+ * hip_stubs.c.
  */
-#include <hip/hip_runtime_api.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+#include "hip_stubs.h"
 
-#include "erasure_code.h"
-#include "isal_hip.h"
-#include "isal_hip_internal.h"
-
-#define CHECK(c)                                                                 \
-        do {                                                                     \
-                if (!(c)) {                                                      \
-                        fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); \
-                        exit(1);                                                 \
-                }                                                                \
-        } while (0)
-
-/* ---- stubs: the HIP runtime and the engine's launcher --------------------- */
+/* ---- stubs: the launchers this program drives ------------------------------ */
 
 static int g_launches;
-
-hipError_t
-hipGetDevice(int *d)
-{
-        *d = 0;
-        return hipSuccess;
-}
-
-hipError_t
-hipMalloc(void **p, size_t n)
-{
-        *p = malloc(n ? n : 1);
-        return *p ? hipSuccess : hipErrorOutOfMemory;
-}
-
-hipError_t
-hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind kind)
-{
-        (void) kind;
-        memcpy(d, s, n);
-        return hipSuccess;
-}
-
-hipError_t
-hipFree(void *p)
-{
-        free(p);
-        return hipSuccess;
-}
-
-int
-isal_hip_dev_enter(int dev)
-{
-        (void) dev;
-        return -1;
-}
-
-void
-isal_hip_dev_leave(int prev)
-{
-        (void) prev;
-}
-
-int
-isal_hip_batch_check_ptrs(const uint64_t *ptrs, size_t n, size_t len, int dev)
-{
-        size_t i;
-        (void) len;
-        (void) dev;
-        for (i = 0; i < n; i++)
-                if (!ptrs[i])
-                        return ISAL_HIP_EINVAL;
-        return ISAL_HIP_OK;
-}
-
-/* coefficient (row l, source j) of the one-pass table image */
-static unsigned char
-coef_of(const uint32_t *tbl, int rows, int l, int j)
-{
-        return (unsigned char) (tbl[((size_t) j * rows + l) * EC_TBL_DWORDS] >> 8); /* entry 1 of c * {0..7} */
-}
 
 /* the mismatch branch, from the location tables alone */
 static unsigned
@@ -142,7 +62,7 @@ isal_hip_launch_locate_batch(const uint64_t *d_ptrs, int ptr_stride, const uint3
         CHECK(ptr_stride == k + rows && em && rows <= EC_MAX_ROWS_PER_PASS);
         for (l = 0; l < rows; l++)
                 for (j = 0; j < k; j++)
-                        CHECK(d_loc[(size_t) l * k + j] == coef_of(d_tbl, rows, l, j));
+                        CHECK(d_loc[(size_t) l * k + j] == coef_of(d_tbl, k, rows, l, j));
         for (s = 0; s < nstripes; s++) {
                 const uint64_t *sp = d_ptrs + s * ptr_stride;
                 verdict[s] = ISAL_HIP_SCRUB_CLEAN;
@@ -152,7 +72,7 @@ isal_hip_launch_locate_batch(const uint64_t *d_ptrs, int ptr_stride, const uint3
                         for (l = 0; l < rows; l++) {
                                 e[l] = ((const unsigned char *) (uintptr_t) sp[k + l])[b];
                                 for (j = 0; j < k; j++)
-                                        e[l] ^= gf_mul(coef_of(d_tbl, rows, l, j),
+                                        e[l] ^= gf_mul(coef_of(d_tbl, k, rows, l, j),
                                                        ((const unsigned char *) (uintptr_t) sp[j])[b]);
                                 any |= e[l];
                         }
@@ -169,23 +89,6 @@ isal_hip_launch_locate_batch(const uint64_t *d_ptrs, int ptr_stride, const uint3
 }
 
 /* ---- the driver ----------------------------------------------------------- */
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-
-static unsigned
-rnd(unsigned n)
-{
-        rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
-        return (unsigned) (rng_state >> 33) % n;
-}
-
-static unsigned char *
-shard(int len)
-{
-        unsigned char *p;
-        CHECK(posix_memalign((void **) &p, 16, (size_t) (len ? len : 1)) == 0);
-        return p;
-}
 
 static void
 make_tables(int cauchy, int k, int rows, unsigned char *a, unsigned char *g)

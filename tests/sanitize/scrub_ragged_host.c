@@ -5,7 +5,7 @@
  * tables, the run of both kinds of object) under ASan + UBSan, as a
  * stand-alone program.
  *
- * The HIP runtime and the kernel launchers are replaced by the stubs below
+ * The HIP runtime (hip_stubs.c) and the kernel launchers (below) are stubs
  * ("device" memory is host memory), so the program needs no GPU and the
  * tables create() uploads can be read back. The launch stub takes every work
  * item from the uploaded item table, checks that the items are the tiles of
@@ -16,127 +16,15 @@
  * the location tables alone, as the kernel's mismatch branch does; the driver
  * compares the verdicts with the corruption it planted.
  *
- * Build and run by hand, from the repository root:
- *   gcc -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=all \
- *       -D__HIP_PLATFORM_AMD__=1 -Iinclude -Iisa-l_amd/csrc -I/opt/rocm/include \
- *       tests/sanitize/scrub_ragged_host.c isa-l_amd/csrc/isal_hip_scrub.c isa-l_amd/csrc/isal_hip_ragged.c \
- *       isa-l_amd/csrc/gf_host.c isa-l_amd/csrc/isal_hip_knobs.c -lpthread \
- *       -o isa-l_amd/build/asan/scrub_ragged_host
- *   isa-l_amd/build/asan/scrub_ragged_host
+ * Built by this directory's Makefile (make -C tests/sanitize) and run by
+ * tests/test_sanitizers_cpu.py; the stubs every such program shares are in
+ * hip_stubs.c.
  */
-#include <hip/hip_runtime_api.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+#include "hip_stubs.h"
 
-#include "erasure_code.h"
-#include "isal_hip.h"
-#include "isal_hip_internal.h"
+/* ---- stubs: the launchers this program drives ------------------------------ */
 
-#define CHECK(c)                                                                 \
-        do {                                                                     \
-                if (!(c)) {                                                      \
-                        fprintf(stderr, "%s:%d: %s\n", __FILE__, __LINE__, #c); \
-                        exit(1);                                                 \
-                }                                                                \
-        } while (0)
-
-/* ---- stubs: the HIP runtime and the engine's launchers -------------------- */
-
-static int g_launches, g_hip_calls;
-static size_t g_check_len[64]; /* the length of each isal_hip_batch_check_ptrs call */
-static int g_checks;
-
-hipError_t
-hipGetDevice(int *d)
-{
-        g_hip_calls++;
-        *d = 0;
-        return hipSuccess;
-}
-
-hipError_t
-hipMalloc(void **p, size_t n)
-{
-        g_hip_calls++;
-        *p = malloc(n ? n : 1);
-        return *p ? hipSuccess : hipErrorOutOfMemory;
-}
-
-hipError_t
-hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind kind)
-{
-        (void) kind;
-        g_hip_calls++;
-        memcpy(d, s, n);
-        return hipSuccess;
-}
-
-hipError_t
-hipFree(void *p)
-{
-        free(p);
-        return hipSuccess;
-}
-
-int
-isal_hip_dev_enter(int dev)
-{
-        (void) dev;
-        return -1;
-}
-
-void
-isal_hip_dev_leave(int prev)
-{
-        (void) prev;
-}
-
-/* one stripe's pointers per call, over that stripe's length */
-int
-isal_hip_batch_check_ptrs(const uint64_t *ptrs, size_t n, size_t len, int dev)
-{
-        size_t i;
-        (void) dev;
-        if (g_checks < 64)
-                g_check_len[g_checks] = len;
-        g_checks++;
-        for (i = 0; i < n; i++)
-                if (!ptrs[i])
-                        return ISAL_HIP_EINVAL;
-        return ISAL_HIP_OK;
-}
-
-/* isal_hip_ragged.c's launchers: never reached from a scrub */
-int
-isal_hip_launch_encode_ragged(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_tbl, const int *d_lens,
-                              const unsigned *d_items, unsigned nitems, const unsigned *d_items_small,
-                              unsigned nitems_small, int k, int rows, void *stream)
-{
-        (void) d_ptrs, (void) ptr_stride, (void) d_tbl, (void) d_lens, (void) d_items, (void) nitems;
-        (void) d_items_small, (void) nitems_small, (void) k, (void) rows, (void) stream;
-        CHECK(!"a scrub launched an encode");
-        return 1;
-}
-
-int
-isal_hip_launch_verify_ragged(const uint64_t *d_ptrs, int ptr_stride, const uint32_t *d_tbl, const int *d_lens,
-                              const unsigned *d_items, unsigned nitems, int k, int rows, long long nstripes,
-                              unsigned long long *bad, void *stream)
-{
-        (void) d_ptrs, (void) ptr_stride, (void) d_tbl, (void) d_lens, (void) d_items, (void) nitems;
-        (void) k, (void) rows, (void) nstripes, (void) bad, (void) stream;
-        CHECK(!"a scrub launched a check");
-        return 1;
-}
-
-/* coefficient (row l, source j) of the one-pass table image */
-static unsigned char
-coef_of(const uint32_t *tbl, int rows, int l, int j)
-{
-        return (unsigned char) (tbl[((size_t) j * rows + l) * EC_TBL_DWORDS] >> 8); /* entry 1 of c * {0..7} */
-}
+static int g_launches;
 
 /* the mismatch branch, from the location tables alone */
 static unsigned
@@ -177,7 +65,7 @@ locate_columns(const uint64_t *sp, const uint32_t *d_tbl, const unsigned char *d
                 for (l = 0; l < rows; l++) {
                         e[l] = ((const unsigned char *) (uintptr_t) sp[k + l])[b];
                         for (j = 0; j < k; j++)
-                                e[l] ^= gf_mul(coef_of(d_tbl, rows, l, j), ((const unsigned char *) (uintptr_t) sp[j])[b]);
+                                e[l] ^= gf_mul(coef_of(d_tbl, k, rows, l, j), ((const unsigned char *) (uintptr_t) sp[j])[b]);
                         any |= e[l];
                 }
                 if (!any)
@@ -224,7 +112,7 @@ isal_hip_launch_locate_ragged(const uint64_t *d_ptrs, int ptr_stride, const uint
         CHECK(ptr_stride == k + rows && rows >= 2 && rows <= EC_MAX_ROWS_PER_PASS && d_items && d_lens);
         for (l = 0; l < rows; l++)
                 for (j = 0; j < k; j++)
-                        CHECK(d_loc[(size_t) l * k + j] == coef_of(d_tbl, rows, l, j));
+                        CHECK(d_loc[(size_t) l * k + j] == coef_of(d_tbl, k, rows, l, j));
         for (s = 0; s < nstripes; s++)
                 verdict[s] = ISAL_HIP_SCRUB_CLEAN;
         /* the items: every tile of every stripe once, in stripe order, none past a length */
@@ -242,23 +130,6 @@ isal_hip_launch_locate_ragged(const uint64_t *d_ptrs, int ptr_stride, const uint
 }
 
 /* ---- the driver ----------------------------------------------------------- */
-
-static uint64_t rng_state = 0x9E3779B97F4A7C15ull;
-
-static unsigned
-rnd(unsigned n)
-{
-        rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
-        return (unsigned) (rng_state >> 33) % n;
-}
-
-static unsigned char *
-shard(int len)
-{
-        unsigned char *p;
-        CHECK(posix_memalign((void **) &p, 16, (size_t) (len ? len : 1)) == 0);
-        return p;
-}
 
 static void
 make_tables(int cauchy, int k, int rows, unsigned char *a, unsigned char *g)

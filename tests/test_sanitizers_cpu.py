@@ -3,6 +3,8 @@
 
   * tests/sanitize/abi_edges.c — every host path of the C ABI with edge
     arguments, checked against the oracle;
+  * tests/sanitize/*_host.c — the host logic of the repair, overwrite, scrub
+    and ragged objects on a stubbed HIP runtime, one program each;
   * the reference's own EC / RAID test programs, compiled with the sanitizers
     and linked against the sanitized engine (isa-l_amd/lib/asan/).
 Both run on the CPU route (no GPU in this tier). Leak checking is on for
@@ -39,6 +41,20 @@ def test_abi_edges_under_asan_ubsan(sanitized_builds):
                        timeout=600, env=SAN_ENV)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
     assert "abi_edges: Pass" in r.stdout
+
+
+# the stripe objects' host sources on a stubbed HIP runtime (tests/sanitize/
+# hip_stubs.c): every create's refusals and uploaded tables, stand-alone
+HOST_PROGRAMS = ["overwrite_host", "overwrite_ragged_host", "ragged_host", "repair_host", "repair_ragged_host",
+                 "scrub_host", "scrub_ragged_host"]
+
+
+@pytest.mark.parametrize("name", HOST_PROGRAMS)
+def test_stripe_object_host_programs_under_asan_ubsan(sanitized_builds, name):
+    r = subprocess.run([os.path.join(ASAN_BUILD, name)], capture_output=True, text=True, timeout=120, env=SAN_ENV)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
+    assert r.stdout.splitlines()[-1].startswith(f"{name}: ok"), r.stdout[-2000:]
+    assert not r.stderr, r.stderr[-4000:]
 
 
 def test_reference_test_programs_under_asan_ubsan(sanitized_builds):
