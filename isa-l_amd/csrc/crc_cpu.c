@@ -3,7 +3,7 @@
  * (crc32_iscsi: include/crc.h:136-150, semantics crc/crc_base.c:205-219;
  * crc64_*: include/crc64.h:54-163, semantics crc/crc64_base.c:569-670) for
  * buffers in host memory. Device-resident buffers go to the GPU checksum
- * kernels instead (isal_hip_shim.c "checksum entry points").
+ * kernels instead (isal_hip_crcapi.c).
  *
  *   CRC32C: from 256 bytes on, the CRC64 section's carry-less folding with
  *           the Castagnoli constants; the rest through the SSE4.2 crc32

@@ -285,7 +285,7 @@ isal_hip_batch_destroy(isal_hip_batch *b)
  * — profiles/r02/r02_crc_tiles_sweep_b.jsonl, r03_crc_tiles_sweep.jsonl), halved
  * while the launch would have fewer than 2048 workgroups.
  * ISAL_HIP_CRC_TILES overrides. Also the drop-in checksum routes' choice
- * (isal_hip_shim.c). */
+ * (isal_hip_crcapi.c). */
 int
 isal_hip_crc_tiles(int len, int nstripes, int def)
 {

@@ -1,7 +1,8 @@
 /*
- * isal_hip_internal.h — contract between the C host shim (isal_hip_shim.c,
- * the batch API in isal_hip_batch.c, gf_host.c) and the HIP kernel launchers
- * (ec_kernels.hip). Not installed.
+ * isal_hip_internal.h — contract between the C host code (the drop-in shim:
+ * isal_hip_shim.c and the units listed in isal_hip_shim.h; the batch API in
+ * isal_hip_batch.c; gf_host.c) and the HIP kernel launchers (ec_kernels.hip).
+ * Not installed.
  *
  * Device argument layout (one contiguous device allocation per call or batch):
  *
@@ -95,7 +96,7 @@ typedef struct {
  * the last one resets *cnt (and *res) for the next call and writes mail[1] =
  * the verify result (*res, ~0 for encode / update), then mail[0] = seq
  * (system-scope stores) into page-locked host memory that the calling thread
- * spins on (isal_hip_shim.c wait_done; ec_kernels.hip karg_done). cnt = NULL:
+ * spins on (isal_hip_karg.c wait_done; ec_kernels.hip karg_done). cnt = NULL:
  * no protocol (the caller synchronises the stream). res: device word a
  * verify's mismatching lanes atomically lower (~0 between calls); NULL for
  * encode / update. */
@@ -409,7 +410,8 @@ unsigned isal_hip_knob_generation(void);
 /* Fault injection (tests): ISAL_HIP_FAULT=<site> makes the HIP call at that
  * site fail as if it had returned an error, without issuing it — the code
  * after the failure then runs for real. Sites 1-5 are those of every
- * GPU-routed drop-in call (isal_hip_shim.c, where the fallback paths run);
+ * GPU-routed drop-in call (isal_hip_stage.c and isal_hip_karg.c; the fallback
+ * paths then run, isal_hip_finish_on_cpu);
  * 6-7 those of isal_hip_batch_set_tables (isal_hip_batch.c). Sites: */
 enum {
         FAULT_NONE = 0,

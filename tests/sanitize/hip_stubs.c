@@ -3,7 +3,10 @@
  * switch and its reachability check as the *_host.c programs see them, the
  * helpers of their drivers, and a default for every kernel launcher the
  * stripe objects' host sources reference. A program defines the launchers it
- * drives; the weak ones here only fail.
+ * drives; the weak ones here only fail. For stage_host.c, which links the
+ * drop-in shim's staging routes and their context: streams, events,
+ * page-locked memory and asynchronous copies, and the plain encode / update /
+ * verify launchers as runs of the CPU route.
  */
 #include "hip_stubs.h"
 
@@ -44,6 +47,183 @@ hipFree(void *p)
         free(p);
         g_allocs--;
         return hipSuccess;
+}
+
+/* ---- streams, events, page-locked memory and asynchronous copies, as the
+ * drop-in shim's staging routes use them (stage_host.c): everything completes
+ * at once, so a stream or an event is only a handle. These are also called by
+ * the routes' worker thread, so they count nothing. */
+
+static char g_handle;
+
+hipError_t
+hipStreamCreate(hipStream_t *s)
+{
+        *s = (hipStream_t) &g_handle;
+        return hipSuccess;
+}
+
+hipError_t
+hipStreamCreateWithFlags(hipStream_t *s, unsigned flags)
+{
+        (void) flags;
+        return hipStreamCreate(s);
+}
+
+hipError_t
+hipStreamDestroy(hipStream_t s)
+{
+        (void) s;
+        return hipSuccess;
+}
+
+hipError_t
+hipStreamSynchronize(hipStream_t s)
+{
+        (void) s;
+        return hipSuccess;
+}
+
+hipError_t
+hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned flags)
+{
+        (void) s, (void) e, (void) flags;
+        return hipSuccess;
+}
+
+hipError_t
+hipEventCreateWithFlags(hipEvent_t *e, unsigned flags)
+{
+        (void) flags;
+        *e = (hipEvent_t) &g_handle;
+        return hipSuccess;
+}
+
+hipError_t
+hipEventDestroy(hipEvent_t e)
+{
+        (void) e;
+        return hipSuccess;
+}
+
+hipError_t
+hipEventRecord(hipEvent_t e, hipStream_t s)
+{
+        (void) e, (void) s;
+        return hipSuccess;
+}
+
+hipError_t
+hipEventSynchronize(hipEvent_t e)
+{
+        (void) e;
+        return hipSuccess;
+}
+
+hipError_t
+hipHostMalloc(void **p, size_t n, unsigned flags)
+{
+        (void) flags;
+        *p = malloc(n);
+        return *p ? hipSuccess : hipErrorOutOfMemory;
+}
+
+hipError_t
+hipHostFree(void *p)
+{
+        free(p);
+        return hipSuccess;
+}
+
+hipError_t
+hipHostGetDevicePointer(void **d, void *h, unsigned flags)
+{
+        (void) flags;
+        *d = h;
+        return hipSuccess;
+}
+
+hipError_t
+hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind kind, hipStream_t stream)
+{
+        (void) kind, (void) stream;
+        memcpy(d, s, n);
+        return hipSuccess;
+}
+
+hipError_t
+hipGetLastError(void)
+{
+        return hipSuccess;
+}
+
+hipError_t
+hipSetDevice(int d)
+{
+        (void) d;
+        return hipSuccess;
+}
+
+/* The plain (uploaded-argument) launchers: the CPU route (ec_cpu.c) over the
+ * "device" pointer table and coefficient tables they are given, at once. A
+ * verify writes two slot words — none, then its first mismatch with the
+ * chunk's first column added — as the real launcher writes one per workgroup. */
+int g_plain_launches;
+
+static unsigned long long
+plain_launch(int op, const uint64_t *d_ptrs, int src0, int nsrc, int dst0, const uint32_t *d_tbl, int len, int k,
+             int rows, int vec_i, int vec16)
+{
+        unsigned char *g = calloc((size_t) 32 * k * rows, 1);
+        unsigned char **p = malloc(sizeof(*p) * (size_t) (nsrc + rows));
+        unsigned long long key;
+        int i, l, j;
+        CHECK(g && p);
+        for (l = 0; l < rows; l++)
+                for (j = 0; j < k; j++)
+                        g[((size_t) l * k + j) * 32 + 1] = coef_of(d_tbl, k, rows, l, j);
+        for (i = 0; i < nsrc + rows; i++) {
+                p[i] = (unsigned char *) (uintptr_t) d_ptrs[i < nsrc ? src0 + i : dst0 + i - nsrc];
+                CHECK(p[i] && (!vec16 || ((uintptr_t) p[i] & 15) == 0));
+        }
+        key = isal_cpu_run(op, 0, len, k, rows, vec_i, g, p, nsrc, p + nsrc);
+        g_plain_launches++;
+        free(g);
+        free(p);
+        return key;
+}
+
+int
+isal_hip_launch_encode(const uint64_t *d_ptrs, int ptr_stride, int src_idx0, int dst_idx0, const uint32_t *d_tbl,
+                       int len, int k, int rows, long long nstripes, int vec16, const isal_hip_encmask *em,
+                       void *stream)
+{
+        CHECK(nstripes == 1 && ptr_stride >= k + rows);
+        (void) plain_launch(ISAL_HIP_OP_ENCODE, d_ptrs, src_idx0, k, dst_idx0, d_tbl, len, k, rows, 0, vec16);
+        return 0;
+}
+
+int
+isal_hip_launch_update(const uint64_t *d_ptrs, int ptr_stride, int src_idx, int dst_idx0, const uint32_t *d_tbl,
+                       int len, int k, int rows, int vec_i, long long nstripes, int vec16, void *stream)
+{
+        CHECK(nstripes == 1 && ptr_stride >= 1 + rows);
+        (void) plain_launch(ISAL_HIP_OP_UPDATE, d_ptrs, src_idx, 1, dst_idx0, d_tbl, len, k, rows, vec_i, vec16);
+        return 0;
+}
+
+int
+isal_hip_launch_verify(const uint64_t *d_ptrs, int ptr_stride, int src_idx0, int dst_idx0, const uint32_t *d_tbl,
+                       int len, int k, int rows, long long col0, unsigned long long *slots, int *nslots, int vec16,
+                       const isal_hip_encmask *em, void *stream)
+{
+        const unsigned long long key =
+                plain_launch(ISAL_HIP_OP_VERIFY, d_ptrs, src_idx0, k, dst_idx0, d_tbl, len, k, rows, 0, vec16);
+        CHECK(ptr_stride >= k + rows);
+        slots[0] = ~0ull;
+        slots[1] = key == ~0ull ? key : key + ((unsigned long long) col0 << 8);
+        *nslots = 2;
+        return 0;
 }
 
 int

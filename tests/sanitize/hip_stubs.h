@@ -3,7 +3,9 @@
  * directory share (hip_stubs.c). Each of them links the stripe objects' host
  * sources (isa-l_amd/csrc/isal_hip_{objects,repair,overwrite,scrub,ragged}.c)
  * against a HIP runtime where "device" memory is host memory, so the program
- * needs no GPU and what a create() uploads can be read back.
+ * needs no GPU and what a create() uploads can be read back. stage_host.c
+ * drives the drop-in shim's staging routes (isal_hip_stage.c, isal_hip_ctx.c)
+ * on the same runtime.
  */
 #ifndef HIP_STUBS_H
 #define HIP_STUBS_H
@@ -31,6 +33,8 @@
 extern int g_hip_calls;
 /* device allocations alive */
 extern int g_allocs;
+/* launches of the stubbed plain launchers (isal_hip_launch_encode / update / verify) */
+extern int g_plain_launches;
 /* reachability queries so far, and the length of each of the first 64 */
 extern int g_checks;
 extern size_t g_check_len[64];

@@ -2430,7 +2430,7 @@ def test_crc64_device_buffer_beyond_one_gib(engine, oracle, gpu):
 
 
 def test_dropin_waits_out_a_slow_stream(engine, oracle, gpu):
-    """The mailbox wait (isal_hip_shim.c wait_done) spins 20 ms, then lets
+    """The mailbox wait (isal_hip_karg.c wait_done) spins 20 ms, then lets
     hipStreamSynchronize finish the call. Here > 30 ms of torch work queued on
     the legacy default stream — ending with the writes of the very source
     shards — holds the engine's blocking stream back: a drop-in encode and a

@@ -4,7 +4,8 @@
   * tests/sanitize/abi_edges.c — every host path of the C ABI with edge
     arguments, checked against the oracle;
   * tests/sanitize/*_host.c — the host logic of the repair, overwrite, scrub
-    and ragged objects on a stubbed HIP runtime, one program each;
+    and ragged objects, and the drop-in shim's staging routes, on a stubbed
+    HIP runtime, one program each;
   * the reference's own EC / RAID test programs, compiled with the sanitizers
     and linked against the sanitized engine (isa-l_amd/lib/asan/).
 Both run on the CPU route (no GPU in this tier). Leak checking is on for
@@ -44,9 +45,11 @@ def test_abi_edges_under_asan_ubsan(sanitized_builds):
 
 
 # the stripe objects' host sources on a stubbed HIP runtime (tests/sanitize/
-# hip_stubs.c): every create's refusals and uploaded tables, stand-alone
+# hip_stubs.c): every create's refusals and uploaded tables, stand-alone; and
+# (stage_host) the drop-in shim's staging routes: every route, whole and after
+# each injected fault, completed on the CPU route
 HOST_PROGRAMS = ["overwrite_host", "overwrite_ragged_host", "ragged_host", "repair_host", "repair_ragged_host",
-                 "scrub_host", "scrub_ragged_host"]
+                 "scrub_host", "scrub_ragged_host", "stage_host"]
 
 
 @pytest.mark.parametrize("name", HOST_PROGRAMS)

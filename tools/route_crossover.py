@@ -6,7 +6,8 @@ plain pageable numpy buffers — what a storage daemon hands the reference) at
 shard lengths from 1 KiB to 16 MiB, forced onto the CPU route
 (ISAL_HIP_BACKEND=cpu, up to 4 MiB) and onto the GPU (=gpu), and prints the per-call times
 and the byte count (k + p) * len where the GPU starts to win. That count is
-DEFAULT_CPU_MAX_BYTES in isal_hip_shim.c. Also times hipPointerGetAttributes,
+DEFAULT_CPU_MAX_BYTES in isal_hip_shim.c (the routing; the staged routes it
+chooses among are in isal_hip_stage.c). Also times hipPointerGetAttributes,
 the per-pointer classification cost every routed call pays. From 1 MiB shards on
 it also times the chunked GPU route one chunk at a time
 (ISAL_HIP_PIPE_CHUNKS=0, the round-2 behaviour) and with page-locked buffers.
