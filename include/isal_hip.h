@@ -505,7 +505,8 @@ int isal_hip_scrub_create_ragged(isal_hip_scrub **out, int k, int rows, const un
  * short: a ragged batch covers nstripes stripes of one geometry (k sources,
  * rows outputs, one matrix), each with its OWN shard length, and encodes or
  * checks all of them with one kernel launch per pass of
- * isal_hip_max_rows_per_pass() rows, on the caller's stream.
+ * isal_hip_max_rows_per_pass() rows, or checksums every shard with two, on the
+ * caller's stream.
  *   gftbls, data (nstripes*k DEVICE pointers), coding (nstripes*rows): as for
  *           isal_hip_batch_create. gftbls is any ec_init_tables output, so a
  *           uniform-pattern decode of ragged stripes is this object built
@@ -551,12 +552,53 @@ int isal_hip_scrub_create_ragged(isal_hip_scrub **out, int k, int rows, const un
  *   workgroup or pass found it. Every word of bad is rewritten by each call,
  *   unless every length is 0 (then nothing is enqueued). Nothing is written
  *   to the shards.
- * Out of scope: update, the fused checksums, the 0/1 XOR form and the
- * LDS-staged and LDS product-table wide kernels of the uniform batch (every
- * pass takes the plain lookup kernel), unaligned or host-pageable shards, any
- * CPU route, and set_tables (one object per matrix). Naming the corrupt shard
- * of a stripe the check reports is isal_hip_scrub_create_ragged above, over
- * the same lens, data and coding.
+ * isal_hip_ragged_crc: the isal_hip_batch_crc contract per stripe (SURVEY
+ *   §8(f): the step storage callers run right after encoding, and the
+ *   confirmation the scrub contract asks for before a named shard is rebuilt).
+ *   crc: DEVICE array of nstripes*(k+rows) words,
+ *     crc[s*(k+rows) + j]     = crc32_iscsi(data[s*k + j],      lens[s], init)
+ *     crc[s*(k+rows) + k + l] = crc32_iscsi(coding[s*rows + l], lens[s], init)
+ *   (the register starts at init, no final inversion). A stripe of length 0
+ *   is not read and its k+rows words are init, which is what crc32_iscsi
+ *   returns for len == 0. Every word of crc is rewritten by each call, unless
+ *   every length is 0: then the call returns 0, enqueues nothing and leaves
+ *   crc untouched, as the check does. Only enqueues, on the caller's stream
+ *   and the object's device: 2 kernel launches (counted by
+ *   isal_hip_kernel_launches), one pass over all shards of all stripes and
+ *   one combine. Idempotent; nothing is written to the shards and nothing is
+ *   read at or past lens[s] of any shard. NULL r or NULL crc: ISAL_HIP_EINVAL,
+ *   nothing enqueued, no HIP call.
+ *   Blocks: a workgroup of the pass covers tt consecutive 4 KiB tiles of one
+ *   shard; tt is one value per object, chosen at its first checksum call:
+ *   ISAL_HIP_CRC_TILES when set (at most 1024), else 64 (256 KiB of a shard,
+ *   the uniform batch's choice), halved while one shard of every stripe
+ *   together has fewer than 2048 blocks. A pass of more than 2^30 work items
+ *   (blocks of one shard of every stripe, times k+rows) is refused with
+ *   ISAL_HIP_EINVAL before anything is allocated or enqueued, not sliced:
+ *   at the default tt that is 256 TiB of shards. create refuses nothing more
+ *   than before.
+ *   Memory: the first checksum call allocates, and destroy frees, a table of
+ *   constants that depends on tt alone, not on any length (45 KiB + 4*tt
+ *   bytes, whatever the number of distinct lengths), 8 bytes per block of one
+ *   shard and 4 per stripe, and the per-lane partials: 1 KiB per block of
+ *   every shard plus 1 KiB per shard (at tt = 64, 1/256 of the shard bytes
+ *   plus 1 KiB per shard). A failed allocation returns ISAL_HIP_ENOMEM or
+ *   ISAL_HIP_EHIP, leaves no HIP error behind and the object as usable for
+ *   encode and check as before.
+ * isal_hip_ragged_encode_crc: isal_hip_ragged_encode, then
+ *   isal_hip_ragged_crc of the sources and the fresh parity, on the same
+ *   stream; any rows, the two-pass case rows > isal_hip_max_rows_per_pass()
+ *   included. NOT fused: its launches are the encode's (one per pass) plus
+ *   the checksum's 2. It exists so that callers write the same sequence as
+ *   with the uniform batch and a one-pass kernel can later slot in behind it.
+ *   The checksum's memory is allocated first: a refusal leaves the parity
+ *   untouched.
+ * Out of scope: update, a one-pass fused encode + checksum, CRC64, the 0/1
+ * XOR form and the LDS-staged and LDS product-table wide kernels of the
+ * uniform batch (every pass takes the plain lookup kernel), unaligned or
+ * host-pageable shards, any CPU route, and set_tables (one object per
+ * matrix). Naming the corrupt shard of a stripe the check reports is
+ * isal_hip_scrub_create_ragged above, over the same lens, data and coding.
  */
 typedef struct isal_hip_ragged isal_hip_ragged;
 long long isal_hip_ragged_items(int nstripes, const int *lens, int tile, unsigned *items);
@@ -565,6 +607,8 @@ int isal_hip_ragged_create(isal_hip_ragged **out, int k, int rows, const unsigne
                            unsigned char *const *coding, int *bad_stripe);
 int isal_hip_ragged_encode(isal_hip_ragged *r, void *stream);
 int isal_hip_ragged_check(isal_hip_ragged *r, unsigned long long *bad, void *stream);
+int isal_hip_ragged_crc(isal_hip_ragged *r, unsigned int init, unsigned int *crc, void *stream);
+int isal_hip_ragged_encode_crc(isal_hip_ragged *r, unsigned int init, unsigned int *crc, void *stream);
 int isal_hip_ragged_destroy(isal_hip_ragged *r);
 
 /* ---- streaming pipeline for HOST-resident stripes ----------------------- */

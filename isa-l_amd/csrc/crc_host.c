@@ -210,6 +210,40 @@ isal_hip_crc32c_plan(long long len, int tt, uint32_t *plan)
                 plan[l] = 0;
 }
 
+/* The ragged checksum's device image (isal_hip_internal.h ISAL_HIP_CRC_RAG_*):
+ * what crc32c_shards_rag and crc32c_combine_rag read, none of it a function
+ * of a length. A shard of any length len = 4096 * nfull + r derives what
+ * isal_hip_crc32c_plan tabulates for it:
+ *   last block   PW[nfull_last]
+ *   W[L]         X[16 * (255 - L) + r]
+ *   Ct[L]        X[max(0, r - 16L - 16)]
+ *   x^(8*len)    X[r] * the product of SQ[i] over the set bits i of nfull
+ * X is built by appending one zero byte at a time (X[n+1] = X[n] * x^8). */
+size_t
+isal_hip_crc32c_ragged_image_dwords(int tt)
+{
+        return (size_t) ISAL_HIP_CRC_RAG_PW + (size_t) tt + 1;
+}
+
+void
+isal_hip_crc32c_ragged_image(int tt, uint32_t *out)
+{
+        uint32_t *x = out + ISAL_HIP_CRC_RAG_X, *sq = out + ISAL_HIP_CRC_RAG_SQ, *pw = out + ISAL_HIP_CRC_RAG_PW;
+        int i;
+        isal_hip_crc32c_tables(out);
+        isal_hip_crc32c_pre_tables(out, out + ISAL_HIP_CRC_RAG_FPRE);
+        mul_tables(isal_hip_crc32c_xpow8n((unsigned long long) ISAL_HIP_CRC_TILE * tt), out + ISAL_HIP_CRC_RAG_BLOCK);
+        x[0] = 0x80000000u;
+        for (i = 1; i < ISAL_HIP_CRC_RAG_X_DWORDS; i++)
+                x[i] = (x[i - 1] >> 8) ^ t0[x[i - 1] & 0xff];
+        sq[0] = isal_hip_crc32c_xpow8n(ISAL_HIP_CRC_TILE);
+        for (i = 1; i < ISAL_HIP_CRC_RAG_SQ_DWORDS; i++)
+                sq[i] = i < ISAL_HIP_CRC_RAG_NSQ ? isal_hip_crc32c_mulmod(sq[i - 1], sq[i - 1]) : 0;
+        pw[0] = 0x80000000u;
+        for (i = 1; i <= tt; i++)
+                pw[i] = isal_hip_crc32c_mulmod(pw[i - 1], sq[0]);
+}
+
 /* The device image (ISAL_HIP_CRC_IMAGE_DWORDS): the part that depends on the
  * length and the geometry, then the whole. */
 void

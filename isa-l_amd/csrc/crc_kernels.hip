@@ -340,6 +340,158 @@ __global__ __launch_bounds__(kBlock) void crc32c_combine(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Ragged: stripe s has its own shard length lens[s] (isal_hip_internal.h
+// "ragged CRC32C"). The pass is crc32c_shards_pre's body with the length, the
+// tile range and the full-tile count read per item: workgroup w takes row
+// w / nsh of the {stripe, block} item table and shard w % nsh of that stripe.
+// Shards are 16-byte aligned by contract; the buffer descriptor of a shard is
+// bounded by its own length, and only whole chunks below it are loaded (the
+// one lane that straddles the length goes byte by byte).
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void crc32c_shards_rag(
+    const uint64_t* __restrict__ ptrs, int nsh, const int* __restrict__ lens,
+    const unsigned* __restrict__ items, unsigned nwork, unsigned tt,
+    const uint32_t* __restrict__ tabs, uint32_t* __restrict__ part, uint32_t* __restrict__ tail) {
+  __shared__ uint32_t lt[kPreFZ + ISAL_HIP_CRC_CHUNK_DWORDS];
+  for (int i = threadIdx.x; i < kPreFZ; i += kBlock) lt[i] = tabs[i];
+  for (int i = threadIdx.x; i < ISAL_HIP_CRC_CHUNK_DWORDS; i += kBlock)
+    lt[kPreFZ + i] = tabs[ISAL_HIP_CRC_RAG_FPRE + i];
+  __syncthreads();
+  const long long lane = threadIdx.x * kVec;
+  auto step = [&](unsigned t, unsigned tf, uint32_t b, const uint4& x) __attribute__((always_inline)) {
+    return t + 1 == tf ? chunk_map(lt + kPreF, x.x ^ b, x.y, x.z, x.w)
+                       : chunk_map(lt + kPreFZ, x.x ^ b, x.y, x.z, x.w);
+  };
+  for (unsigned w = blockIdx.x; w < nwork; w += gridDim.x) {
+    const unsigned item = w / nsh, i = w - item * nsh;
+    const unsigned stripe = items[2 * static_cast<size_t>(item)], blk = items[2 * static_cast<size_t>(item) + 1];
+    const int len = lens[stripe];
+    const uint64_t base = ptrs[static_cast<size_t>(stripe) * nsh + i];
+    const unsigned nfull = static_cast<unsigned>(len) / kTile;
+    const unsigned ntiles = nfull + (static_cast<unsigned>(len) % kTile ? 1u : 0u);
+    const unsigned t0 = blk * tt, t1 = t0 + tt < ntiles ? t0 + tt : ntiles;
+    const unsigned tf = t1 < nfull ? t1 : nfull;  // full tiles of this block
+    uint32_t b = 0;
+    unsigned t = t0;
+    uint4 xn[kCrcBatch];
+    if (t + kCrcBatch <= tf) {
+#pragma unroll
+      for (unsigned g = 0; g < kCrcBatch; ++g)
+        xn[g] = load16<kBufNT>(base, static_cast<long long>(t + g) * kTile + lane, len);
+    }
+    for (; t + kCrcBatch <= tf; t += kCrcBatch) {
+      uint4 x[kCrcBatch];
+#pragma unroll
+      for (unsigned g = 0; g < kCrcBatch; ++g) x[g] = xn[g];
+      if (t + 2 * kCrcBatch <= tf) {
+#pragma unroll
+        for (unsigned g = 0; g < kCrcBatch; ++g)
+          xn[g] = load16<kBufNT>(base, static_cast<long long>(t + kCrcBatch + g) * kTile + lane, len);
+      }
+#pragma unroll
+      for (unsigned g = 0; g < kCrcBatch; ++g) b = step(t + g, tf, b, x[g]);
+    }
+    for (; t < tf; ++t) b = step(t, tf, b, load16<kBufNT>(base, static_cast<long long>(t) * kTile + lane, len));
+    if (tf < t1) {  // the ragged tile: its chunk CRCs go to the shard's tail slot
+      const long long off = static_cast<long long>(tf) * kTile + lane;
+      const long long left = len - off;
+      const int nb = left >= kVec ? kVec : (left > 0 ? static_cast<int>(left) : 0);
+      uint32_t c = 0;
+      if (nb == kVec) {
+        const uint4 x = load16<kBufNT>(base, off, len);
+        c = chunk_map(lt + kPreF, x.x, x.y, x.z, x.w);
+      } else if (nb > 0) {
+        c = bytes_crc(lt, reinterpret_cast<const uint8_t*>(base) + off, nb);
+      }
+      tail[(static_cast<size_t>(stripe) * nsh + i) * kBlock + threadIdx.x] = c;
+    }
+    part[static_cast<size_t>(w) * kBlock + threadIdx.x] = b;
+  }
+}
+
+// The product over the wave of v (every lane holds a factor; 1 = 0x80000000).
+__device__ __forceinline__ uint32_t wave_product32(uint32_t v) {
+#pragma unroll
+  for (int m = 16; m >= 1; m >>= 1) v = crc_mulmod(v, __shfl_xor(v, m, 64));
+  return v;
+}
+
+// Ragged combine: crc32c_combine with every per-length constant derived from
+// the length-independent image (crc_host.c isal_hip_crc32c_ragged_image). One
+// wave per shard, lane l on lane positions 4l .. 4l + 3:
+//  1. Horner over the shard's own nblk blocks through the LDS byte tables of
+//     x^(8*4096*tt);
+//  2. the last block's multiplier PW[nfull_last], W[L] = X[16(255-L) + r],
+//     Ct[L] = X[max(0, r - 16L - 16)] and x^(8*len) = X[r] * prod SQ[i] over
+//     the set bits i of nfull (lane i < 19 holds factor i: five wave steps);
+//  3. the wave XOR-reduction;
+//  4. ^ init * x^(8*len). A shard of length 0 is init.
+__global__ __launch_bounds__(kBlock) void crc32c_combine_rag(
+    const uint32_t* __restrict__ part, const uint32_t* __restrict__ tail,
+    const uint32_t* __restrict__ image, const int* __restrict__ lens,
+    const unsigned* __restrict__ first, unsigned nsh, unsigned tt, unsigned init,
+    uint32_t* __restrict__ out, unsigned nshards) {
+  constexpr unsigned kWaves = kBlock / 64;
+  __shared__ uint32_t kt[1024];  // byte tables of x^(8*4096*tt)
+  for (int i = threadIdx.x; i < 1024; i += kBlock) kt[i] = image[ISAL_HIP_CRC_RAG_BLOCK + i];
+  __syncthreads();
+  const unsigned lane = threadIdx.x & 63;
+  const uint32_t* __restrict__ X = image + ISAL_HIP_CRC_RAG_X;
+  const uint32_t sq = lane < ISAL_HIP_CRC_RAG_NSQ ? image[ISAL_HIP_CRC_RAG_SQ + lane] : 0x80000000u;
+  for (unsigned sh = blockIdx.x * kWaves + (threadIdx.x >> 6); sh < nshards; sh += gridDim.x * kWaves) {
+    const unsigned stripe = sh / nsh, i = sh - stripe * nsh;
+    const unsigned len = static_cast<unsigned>(lens[stripe]);
+    if (len == 0) {  // wave-uniform
+      if (lane == 0) out[sh] = init;
+      continue;
+    }
+    const unsigned nfull = len / kTile, r = len % kTile;
+    const unsigned ntiles = nfull + (r ? 1u : 0u), nblk = (ntiles + tt - 1) / tt;
+    const unsigned done = (nblk - 1) * tt;  // tiles before the last block
+    const unsigned nfull_last = nfull > done ? nfull - done : 0u;
+    const uint32_t* pp = part + (static_cast<size_t>(first[stripe]) * nsh + i) * kBlock + 4 * lane;
+    const size_t bstride = static_cast<size_t>(nsh) * kBlock;
+    uint32_t h[4] = {0, 0, 0, 0};
+    for (unsigned b = 0; b + 1 < nblk; ++b) {
+      const uint4 p = *reinterpret_cast<const uint4*>(pp + b * bstride);
+      const uint32_t pv[4] = {p.x, p.y, p.z, p.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        h[j] = xor3(kt[h[j] & 0xff], kt[256 + ((h[j] >> 8) & 0xff)], kt[512 + ((h[j] >> 16) & 0xff)]) ^
+               kt[768 + (h[j] >> 24)] ^ pv[j];
+    }
+    {  // the last block: nfull_last <= tt full tiles
+      const uint4 p = *reinterpret_cast<const uint4*>(pp + (nblk - 1) * bstride);
+      const uint32_t pv[4] = {p.x, p.y, p.z, p.w};
+      if (nblk > 1) {  // wave-uniform; h is 0 before a shard's only block
+        const uint32_t klast = image[ISAL_HIP_CRC_RAG_PW + nfull_last];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) h[j] = crc_mulmod(h[j], klast) ^ pv[j];
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) h[j] = pv[j];
+      }
+    }
+    uint32_t v = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v ^= crc_mulmod(h[j], X[16 * (255 - (4 * lane + j)) + r]);
+    if (r) {  // wave-uniform
+      const uint4 t = reinterpret_cast<const uint4*>(tail + static_cast<size_t>(sh) * kBlock)[lane];
+      const uint32_t tv[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int rest = static_cast<int>(r) - 16 * static_cast<int>(4 * lane + j) - 16;
+        v ^= crc_mulmod(tv[j], X[rest > 0 ? rest : 0]);
+      }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v ^= __shfl_xor(v, m, 64);
+    const uint32_t xfull = wave_product32(((nfull >> (lane & 31)) & 1u) ? sq : 0x80000000u);
+    if (lane == 0) out[sh] = v ^ crc_mulmod(init, crc_mulmod(xfull, X[r]));
+  }
+}
+
 constexpr unsigned kMaxCrcItems = 1u << 30;
 
 unsigned crc_grid(unsigned long long nitems) {
@@ -837,6 +989,37 @@ extern "C" int isal_hip_launch_crc_combine(const uint32_t* d_part, const uint32_
   const unsigned grid = want < 2048 ? static_cast<unsigned>(want) : 2048u;
   ISAL_LAUNCH(crc32c_combine, dim3(grid), dim3(kBlock), 0, s, d_part, d_tail, d_plan,
                      static_cast<unsigned>(nblk), has_tail, init, out, static_cast<unsigned>(nsh));
+  isal_hip_count_launch();
+  return static_cast<int>(hipGetLastError());
+}
+
+extern "C" int isal_hip_launch_crc_ragged(const uint64_t* d_ptrs, int nsh, const int* d_lens,
+                                          const unsigned* d_items, unsigned nitems, int tt,
+                                          const uint32_t* d_image, uint32_t* d_part, uint32_t* d_tail,
+                                          void* stream) {
+  if (nitems == 0 || nsh <= 0) return 0;
+  const unsigned long long nwork = static_cast<unsigned long long>(nitems) * static_cast<unsigned>(nsh);
+  if (nwork > kMaxCrcItems || tt < 1) return static_cast<int>(hipErrorInvalidValue);
+  ISAL_LAUNCH(crc32c_shards_rag, dim3(crc_grid(nwork)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
+              d_ptrs, nsh, d_lens, d_items, static_cast<unsigned>(nwork), static_cast<unsigned>(tt), d_image,
+              d_part, d_tail);
+  isal_hip_count_launch();
+  return static_cast<int>(hipGetLastError());
+}
+
+extern "C" int isal_hip_launch_crc_combine_ragged(const uint32_t* d_part, const uint32_t* d_tail,
+                                                  const uint32_t* d_image, const int* d_lens,
+                                                  const unsigned* d_first, int nsh, int tt,
+                                                  unsigned int init, uint32_t* out, long long nstripes,
+                                                  void* stream) {
+  if (nstripes <= 0 || nsh <= 0) return 0;
+  const unsigned long long nshards = static_cast<unsigned long long>(nstripes) * static_cast<unsigned>(nsh);
+  if (nshards > 0xFFFFFFFFull || tt < 1) return static_cast<int>(hipErrorInvalidValue);
+  const unsigned long long want = (nshards + 3) / 4;  // four shards per workgroup
+  const unsigned grid = want < 2048 ? static_cast<unsigned>(want) : 2048u;
+  ISAL_LAUNCH(crc32c_combine_rag, dim3(grid), dim3(kBlock), 0, static_cast<hipStream_t>(stream), d_part,
+              d_tail, d_image, d_lens, d_first, static_cast<unsigned>(nsh), static_cast<unsigned>(tt), init,
+              out, static_cast<unsigned>(nshards));
   isal_hip_count_launch();
   return static_cast<int>(hipGetLastError());
 }

@@ -498,6 +498,67 @@ typedef struct {
         long long nfull_last; /* full tiles in the last workgroup */
 } isal_hip_crc_geom;
 
+/* ---- ragged CRC32C (isal_hip_ragged_crc; crc_kernels.hip crc32c_shards_rag,
+ * crc32c_combine_rag) ---------------------------------------------------------
+ * Stripe s has its own shard length lens[s]; the block size tt (tiles per
+ * workgroup) is one per object. Stripe s has ceil(ceil(lens[s]/4096)/tt)
+ * blocks, and the item table isal_hip_ragged_items(nstripes, lens, 4096*tt)
+ * lists them as {stripe, block}; first[s] (nstripes + 1 words) is the row of
+ * stripe s's block 0. A work item of the pass is (row w of that table, shard
+ * i < nsh = k + rows); it leaves
+ *   part[(w * nsh + i) * 256 + L]          the chain of lane L over the block's
+ *                                          full tiles
+ *   tail[(stripe * nsh + i) * 256 + L]     the crc of lane L's chunk of the
+ *                                          ragged tile (lens[s] % 4096 != 0)
+ * The image (isal_hip_crc32c_ragged_image) depends on tt alone:
+ *   [0, TAB_DWORDS)   isal_hip_crc32c_tables (T0, F, Z^4096)
+ *   RAG_FPRE          F' (isal_hip_crc32c_pre_tables)
+ *   RAG_BLOCK         byte tables of x^(8*4096*tt)       (Horner across blocks)
+ *   RAG_X             X[n] = x^(8n), n < 8192            (W, Ct, the tail of x^(8*len))
+ *   RAG_SQ            x^(8*4096*2^i), i < 19             (x^(8*len) by square-and-multiply:
+ *                                                         len < 2^31 has fewer than 2^19 tiles)
+ *   RAG_PW            x^(8*4096*j), j = 0..tt            (the last block's full tiles) */
+#define ISAL_HIP_CRC_RAG_FPRE ISAL_HIP_CRC_TAB_DWORDS
+#define ISAL_HIP_CRC_RAG_BLOCK (ISAL_HIP_CRC_RAG_FPRE + ISAL_HIP_CRC_FPRE_DWORDS)
+#define ISAL_HIP_CRC_RAG_X (ISAL_HIP_CRC_RAG_BLOCK + 1024)
+#define ISAL_HIP_CRC_RAG_X_DWORDS (2 * ISAL_HIP_CRC_TILE)
+#define ISAL_HIP_CRC_RAG_SQ (ISAL_HIP_CRC_RAG_X + ISAL_HIP_CRC_RAG_X_DWORDS)
+#define ISAL_HIP_CRC_RAG_NSQ 19
+#define ISAL_HIP_CRC_RAG_SQ_DWORDS 32 /* a wave's lanes 0..31 read one word each */
+#define ISAL_HIP_CRC_RAG_PW (ISAL_HIP_CRC_RAG_SQ + ISAL_HIP_CRC_RAG_SQ_DWORDS)
+#define ISAL_HIP_CRC_RAG_MAX_TT 1024 /* ISAL_HIP_CRC_TILES is clamped to this */
+/* The ragged batch object (isal_hip_ragged.c; its checksum state is
+ * isal_hip_ragged_crc.c's). */
+struct isal_hip_ragged {
+        int k, rows, nstripes, device;
+        unsigned nitems[NTILES];
+        uint64_t *d_ptrs;
+        uint32_t *d_tbl;
+        int *d_lens;
+        unsigned *d_items[NTILES];
+        /* the checksums' own state (isal_hip_ragged_crc): the lengths as
+         * create saw them, then what the first checksum call allocates */
+        int *h_lens;
+        int crc_tt;
+        unsigned crc_nitems;
+        uint32_t *d_crc, *d_part, *d_tail;
+        unsigned *d_crc_items, *d_crc_first;
+};
+/* isal_hip_ragged_encode's body, for a caller already on the object's device */
+int isal_hip_ragged_encode_on_device(struct isal_hip_ragged *r, void *stream);
+size_t isal_hip_crc32c_ragged_image_dwords(int tt);
+void isal_hip_crc32c_ragged_image(int tt, uint32_t *out);
+/* One launch over nitems * nsh work items (at most ISAL_HIP_RAGGED_MAX_ITEMS:
+ * hipErrorInvalidValue past it, nothing enqueued); nothing when nitems == 0. */
+int isal_hip_launch_crc_ragged(const uint64_t *d_ptrs, int nsh, const int *d_lens, const unsigned *d_items,
+                               unsigned nitems, int tt, const uint32_t *d_image, uint32_t *d_part,
+                               uint32_t *d_tail, void *stream);
+/* out[stripe * nsh + i] = crc32_iscsi(shard, lens[stripe], init); init for a
+ * stripe of length 0. One launch. */
+int isal_hip_launch_crc_combine_ragged(const uint32_t *d_part, const uint32_t *d_tail, const uint32_t *d_image,
+                                       const int *d_lens, const unsigned *d_first, int nsh, int tt,
+                                       unsigned int init, uint32_t *out, long long nstripes, void *stream);
+
 /* Tiles per CRC workgroup (CRC32C and CRC64) of a launch over nstripes
  * stripes of len-byte shards: def, halved for small launches;
  * ISAL_HIP_CRC_TILES overrides (isal_hip_batch.c). */

@@ -20,7 +20,9 @@
  *   3. gftbls becomes the encode's device coefficient tables; the item tables
  *      are built at the upload, once the shards are known to be reachable.
  * A ragged batch belongs to the device that was current when it was created
- * (ON_BATCH_DEVICE).
+ * (ON_BATCH_DEVICE). The object's layout is in isal_hip_internal.h: its
+ * fragment checksums are isal_hip_ragged_crc.c's, which builds what it needs
+ * at the first checksum call from the lengths create keeps (h_lens).
  */
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -30,15 +32,6 @@
 #include "erasure_code.h"
 #include "isal_hip.h"
 #include "isal_hip_internal.h"
-
-struct isal_hip_ragged {
-        int k, rows, nstripes, device;
-        unsigned nitems[NTILES];
-        uint64_t *d_ptrs;
-        uint32_t *d_tbl;
-        int *d_lens;
-        unsigned *d_items[NTILES];
-};
 
 long long
 isal_hip_ragged_items(int nstripes, const int *lens, int tile, unsigned *items)
@@ -125,10 +118,13 @@ isal_hip_ragged_create(isal_hip_ragged **out, int k, int rows, const unsigned ch
          * at the upload) */
         h_tbl = (uint32_t *) malloc(isal_hip_tables_dwords(k, rows) * 4);
         r = (isal_hip_ragged *) calloc(1, sizeof(*r));
-        if (!h_tbl || !r) {
+        if (r)
+                r->h_lens = (int *) malloc((size_t) nstripes * sizeof(int));
+        if (!h_tbl || !r || !r->h_lens) {
                 ret = ISAL_HIP_ENOMEM;
                 goto done;
         }
+        memcpy(r->h_lens, lens, (size_t) nstripes * sizeof(int));
         isal_hip_build_tables(k, rows, gftbls, h_tbl);
         r->k = k;
         r->rows = rows;
@@ -148,8 +144,8 @@ done:
         return ISAL_HIP_OK;
 }
 
-static int
-ragged_encode_impl(isal_hip_ragged *r, void *stream)
+int
+isal_hip_ragged_encode_on_device(isal_hip_ragged *r, void *stream)
 {
         return isal_hip_launch_encode_ragged(r->d_ptrs, r->k + r->rows, r->d_tbl, r->d_lens, r->d_items[TILE_BIG],
                                              r->nitems[TILE_BIG], r->d_items[TILE_SMALL], r->nitems[TILE_SMALL],
@@ -161,7 +157,7 @@ ragged_encode_impl(isal_hip_ragged *r, void *stream)
 int
 isal_hip_ragged_encode(isal_hip_ragged *r, void *stream)
 {
-        ON_BATCH_DEVICE(r, ragged_encode_impl(r, stream));
+        ON_BATCH_DEVICE(r, isal_hip_ragged_encode_on_device(r, stream));
 }
 
 static int
@@ -187,6 +183,12 @@ isal_hip_ragged_destroy(isal_hip_ragged *r)
         int t;
         if (!r)
                 return ISAL_HIP_OK;
+        /* what the first checksum call allocated (isal_hip_ragged_crc.c) */
+        isal_hip_obj_drop(r->d_crc);
+        isal_hip_obj_drop(r->d_part);
+        isal_hip_obj_drop(r->d_crc_items);
+        isal_hip_obj_drop(r->d_crc_first);
+        free(r->h_lens);
         isal_hip_obj_drop(r->d_ptrs);
         isal_hip_obj_drop(r->d_tbl);
         isal_hip_obj_drop(r->d_lens);

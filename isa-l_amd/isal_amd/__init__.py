@@ -137,6 +137,8 @@ def lib() -> ctypes.CDLL:
                                            _u8pp, _u8pp, ctypes.POINTER(ctypes.c_int)]),
             "isal_hip_ragged_encode": (i, [ctypes.c_void_p, ctypes.c_void_p]),
             "isal_hip_ragged_check": (i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+            "isal_hip_ragged_crc": (i, [ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]),
+            "isal_hip_ragged_encode_crc": (i, [ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]),
             "isal_hip_ragged_destroy": (i, [ctypes.c_void_p]),
             "isal_hip_pipe_create": (i, [ctypes.POINTER(ctypes.c_void_p), i, i, i, _u8p, i, i]),
             "isal_hip_pipe_submit": (i, [ctypes.c_void_p, _u8pp, _u8pp]),
@@ -678,9 +680,9 @@ class Ragged:
     ragged batch).
 
     data[s*k + j] / coding[s*rows + l] are addresses (or tensors) of 16-byte
-    aligned device buffers, as for Batch. encode() and check() only enqueue on
-    `stream`; check() fills the DEVICE buffer bad (one uint64 per stripe) as
-    Batch.check does, ~0 for a stripe of length 0."""
+    aligned device buffers, as for Batch. encode(), check(), crc() and
+    encode_crc() only enqueue on `stream`; check() fills the DEVICE buffer bad
+    (one uint64 per stripe) as Batch.check does, ~0 for a stripe of length 0."""
 
     def __init__(self, k: int, rows: int, gftbls, lens: Sequence[int], data: Sequence, coding: Sequence):
         ln = np.array(list(lens), dtype=np.int32)
@@ -705,6 +707,23 @@ class Ragged:
         rc = lib().isal_hip_ragged_check(self._h, ctypes.c_void_p(addr(bad)), ctypes.c_void_p(stream))
         if rc != 0:
             raise RuntimeError(f"isal_hip_ragged_check failed ({rc})")
+
+    def crc(self, init: int, crc, stream: int = 0) -> None:
+        """crc32_iscsi(shard, lens[s], init) of every source and parity shard
+        into the DEVICE buffer crc (nstripes*(k+rows) uint32, stripe-major,
+        sources then parity, as Batch.crc); a stripe of length 0 yields init."""
+        rc = lib().isal_hip_ragged_crc(self._h, init & 0xFFFFFFFF, ctypes.c_void_p(addr(crc)),
+                                       ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_ragged_crc failed ({rc})")
+
+    def encode_crc(self, init: int, crc, stream: int = 0) -> None:
+        """encode(), then crc() of the sources and the fresh parity on the same
+        stream (not fused: the encode's launches plus the checksum's)."""
+        rc = lib().isal_hip_ragged_encode_crc(self._h, init & 0xFFFFFFFF, ctypes.c_void_p(addr(crc)),
+                                              ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_ragged_encode_crc failed ({rc})")
 
     def close(self) -> None:
         if getattr(self, "_h", None):
