@@ -593,11 +593,51 @@ int isal_hip_scrub_create_ragged(isal_hip_scrub **out, int k, int rows, const un
  *   with the uniform batch and a one-pass kernel can later slot in behind it.
  *   The checksum's memory is allocated first: a refusal leaves the parity
  *   untouched.
- * Out of scope: update, a one-pass fused encode + checksum, CRC64, the 0/1
- * XOR form and the LDS-staged and LDS product-table wide kernels of the
- * uniform batch (every pass takes the plain lookup kernel), unaligned or
- * host-pageable shards, any CPU route, and set_tables (one object per
- * matrix). Naming the corrupt shard of a stripe the check reports is
+ * isal_hip_ragged_crc64: isal_hip_ragged_crc for the eight crc64_* flavours,
+ *   with isal_hip_batch_crc64's semantics per stripe (the Rocksoft reflected
+ *   flavour is the NVMe / S3 CRC64NVME checksum). variant is an
+ *   ISAL_HIP_CRC64_* value; crc: DEVICE array of nstripes*(k+rows) 64-bit
+ *   words,
+ *     crc[s*(k+rows) + j]     = crc64_<variant>(init, data[s*k + j],      lens[s])
+ *     crc[s*(k+rows) + k + l] = crc64_<variant>(init, coding[s*rows + l], lens[s])
+ *   (the register starts at ~init and is inverted on return). A stripe of
+ *   length 0 is not read and its k+rows words are init, which is what
+ *   crc64_* returns for len == 0. Every word of crc is rewritten by each call,
+ *   unless every length is 0: then the call returns 0, enqueues nothing and
+ *   leaves crc untouched. Only enqueues, on the caller's stream and the
+ *   object's device, whatever the calling thread's current device: 2 kernel
+ *   launches (counted by isal_hip_kernel_launches), one pass and one combine.
+ *   Idempotent; nothing is written to the shards and nothing is read at or
+ *   past lens[s] of any shard. NULL r, NULL crc or a variant outside
+ *   [0, ISAL_HIP_CRC64_NVARIANTS): ISAL_HIP_EINVAL, nothing enqueued, no HIP
+ *   call.
+ *   Blocks: tt as for isal_hip_ragged_crc, but CRC64's own value, chosen at
+ *   the object's first CRC64 call: ISAL_HIP_CRC_TILES when set (at most 1024),
+ *   else 128 (the uniform checksum-only CRC64's choice), halved while one
+ *   shard of every stripe together has fewer than 2048 blocks. A pass of more
+ *   than 2^30 work items (blocks of one shard of every stripe, times k+rows)
+ *   is refused with ISAL_HIP_EINVAL before anything is allocated or enqueued.
+ *   Memory, all of it CRC64's own and independent of what isal_hip_ragged_crc
+ *   keeps, freed by destroy: the first CRC64 call allocates 8 bytes per block
+ *   of one shard and 4 per stripe, and the per-lane partials, 2 KiB per block
+ *   of every shard (at tt = 128, 1/256 of the shard bytes), shared by all
+ *   variants; the first call with a given variant builds and uploads that
+ *   variant's table of constants, which depends on the variant and tt alone,
+ *   not on any length: 8*(11104 + tt + 1) bytes (87.8 KiB at tt = 128,
+ *   whatever the number of distinct lengths; the uniform batch uploads about
+ *   80 KiB per variant for ONE length). A failed allocation returns
+ *   ISAL_HIP_ENOMEM or ISAL_HIP_EHIP, leaves no HIP error behind and the
+ *   object as usable for encode, check and isal_hip_ragged_crc as before.
+ * isal_hip_ragged_encode_crc64: isal_hip_ragged_encode, then
+ *   isal_hip_ragged_crc64, on the same stream, for any rows. Not a fused
+ *   pass either: its launches are the encode's (one per pass) plus 2. The
+ *   checksum's memory and the variant's table are set up first: a refusal
+ *   leaves the parity untouched.
+ * Out of scope: update, a one-pass fused encode + checksum, CRC64 fused into
+ * the encode, the 0/1 XOR form and the LDS-staged and LDS product-table wide
+ * kernels of the uniform batch (every pass takes the plain lookup kernel),
+ * unaligned or host-pageable shards, any CPU route, and set_tables (one
+ * object per matrix). Naming the corrupt shard of a stripe the check reports is
  * isal_hip_scrub_create_ragged above, over the same lens, data and coding.
  */
 typedef struct isal_hip_ragged isal_hip_ragged;
@@ -609,6 +649,10 @@ int isal_hip_ragged_encode(isal_hip_ragged *r, void *stream);
 int isal_hip_ragged_check(isal_hip_ragged *r, unsigned long long *bad, void *stream);
 int isal_hip_ragged_crc(isal_hip_ragged *r, unsigned int init, unsigned int *crc, void *stream);
 int isal_hip_ragged_encode_crc(isal_hip_ragged *r, unsigned int init, unsigned int *crc, void *stream);
+int isal_hip_ragged_crc64(isal_hip_ragged *r, int variant, unsigned long long init,
+                          unsigned long long *crc, void *stream);
+int isal_hip_ragged_encode_crc64(isal_hip_ragged *r, int variant, unsigned long long init,
+                                 unsigned long long *crc, void *stream);
 int isal_hip_ragged_destroy(isal_hip_ragged *r);
 
 /* ---- streaming pipeline for HOST-resident stripes ----------------------- */

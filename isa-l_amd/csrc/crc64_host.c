@@ -330,6 +330,128 @@ isal_hip_crc64_cpu_tables(int variant, uint64_t byte[256], uint64_t slice[8 * 25
                 }
 }
 
+/* ---- the quotient ring (ragged CRC64, isal_hip_internal.h "ragged CRC64") ---
+ * A raw register is a polynomial over GF(2) modulo the flavour's P(x) of
+ * degree 64: bit i is the coefficient of x^i for the norm flavours and of
+ * x^(63-i) for the refl ones (the bit-reversed order). Z^n is multiplication
+ * by x^(8n) in that ring, so the constants of any length are products of a few
+ * ring elements that depend on no length. */
+static uint64_t
+ring_poly(int variant)
+{
+        return isal_hip_crc64_is_refl(variant) ? bitrev64(poly_norm[variant >> 1]) : poly_norm[variant >> 1];
+}
+
+/* the ring's 1 */
+static uint64_t
+ring_one(int variant)
+{
+        return isal_hip_crc64_is_refl(variant) ? 1ULL << 63 : 1ULL;
+}
+
+/* What the ragged combine multiplies with: P(x) without x^64, in the
+ * register's bit order. */
+uint64_t
+isal_hip_crc64_ring_poly(int variant)
+{
+        return ring_poly(variant);
+}
+
+/* a * b mod P: b is multiplied by x once per coefficient of a, lowest first. */
+uint64_t
+isal_hip_crc64_mulmod(int variant, uint64_t a, uint64_t b)
+{
+        const int refl = isal_hip_crc64_is_refl(variant);
+        const uint64_t p = ring_poly(variant);
+        uint64_t r = 0;
+        int i;
+        for (i = 0; i < 64; i++) {
+                if (refl) {
+                        if (a >> 63)
+                                r ^= b;
+                        a <<= 1;
+                        b = (b & 1) ? (b >> 1) ^ p : b >> 1;
+                } else {
+                        if (a & 1)
+                                r ^= b;
+                        a >>= 1;
+                        b = (b >> 63) ? (b << 1) ^ p : b << 1;
+                }
+        }
+        return r;
+}
+
+/* x^(8n) mod P: the multiplier of "append n zero bytes" (square and multiply
+ * from x^8 = one zero byte appended to 1). */
+uint64_t
+isal_hip_crc64_xpow8n(int variant, unsigned long long n)
+{
+        uint64_t r = ring_one(variant), sq = raw_update(variant, r, NULL, 1);
+        for (; n; n >>= 1) {
+                if (n & 1)
+                        r = isal_hip_crc64_mulmod(variant, r, sq);
+                sq = isal_hip_crc64_mulmod(variant, sq, sq);
+        }
+        return r;
+}
+
+/* The ragged checksum's device image (isal_hip_internal.h ISAL_HIP_CRC64_RAG_*):
+ * what crc64_shards_rag and crc64_combine_rag read, a function of (variant,
+ * tt) alone. A shard of any length len = 4096 * nfull + 16 * q + rem derives
+ * what isal_hip_crc64_len_tables tabulates for it:
+ *   OP_LAST   multiplication by PW[nfull_last]
+ *   OP_TAIL   multiplication by X[16 * q]
+ *   x^(8*len) X[len % 4096] * the product of SQ[i] over the set bits i of nfull
+ * X is built by appending one zero byte at a time. */
+size_t
+isal_hip_crc64_ragged_image_entries(int tt)
+{
+        return (size_t) ISAL_HIP_CRC64_RAG_PW + (size_t) tt + 1;
+}
+
+void
+isal_hip_crc64_ragged_image(int variant, int tt, uint64_t *out)
+{
+        uint64_t basis[128], bu[128], bz[128], m[64];
+        uint64_t *x = out + ISAL_HIP_CRC64_RAG_X, *sq = out + ISAL_HIP_CRC64_RAG_SQ, *pw = out + ISAL_HIP_CRC64_RAG_PW;
+        uint8_t chunk[16];
+        int b, j, s;
+        /* BYTE, CHUNK, OP_TREE and PRE as isal_hip_crc64_tables builds them */
+        for (b = 0; b < 256; b++)
+                out[ISAL_HIP_CRC64_RAG_BYTE + b] =
+                        raw_update(variant, isal_hip_crc64_is_refl(variant) ? (uint64_t) b : (uint64_t) b << 56, NULL, 1);
+        for (j = 0; j < 128; j++) {
+                memset(chunk, 0, sizeof(chunk));
+                chunk[j / 8] = (uint8_t) (1u << (j % 8));
+                basis[j] = raw_update(variant, 0, chunk, 16);
+        }
+        chunk_tables(basis, out + ISAL_HIP_CRC64_RAG_CHUNK);
+        isal_hip_crc64_zpow(variant, (unsigned long long) ISAL_HIP_CRC_TILE * tt, m);
+        op_tables(m, out + ISAL_HIP_CRC64_RAG_BLOCK);
+        for (s = 0; s < 8; s++) {
+                isal_hip_crc64_zpow(variant, 16ULL << s, m);
+                op_tables(m, out + ISAL_HIP_CRC64_RAG_TREE + s * ISAL_HIP_CRC64_OP_ENTRIES);
+        }
+        isal_hip_crc64_zpow(variant, ISAL_HIP_CRC_TILE - 16, m);
+        for (j = 0; j < 128; j++) {
+                bu[j] = pi_of(variant, basis[j]);
+                bz[j] = pi_of(variant, apply(m, basis[j]));
+        }
+        chunk_tables(bu, out + ISAL_HIP_CRC64_RAG_PRE);
+        chunk_tables(bz, out + ISAL_HIP_CRC64_RAG_PRE + ISAL_HIP_CRC64_CHUNK_ENTRIES);
+        /* the ring elements */
+        x[0] = ring_one(variant);
+        for (j = 1; j < ISAL_HIP_CRC64_RAG_X_ENTRIES; j++)
+                x[j] = raw_update(variant, x[j - 1], NULL, 1);
+        sq[0] = isal_hip_crc64_xpow8n(variant, ISAL_HIP_CRC_TILE);
+        for (j = 1; j < ISAL_HIP_CRC64_RAG_SQ_ENTRIES; j++)
+                sq[j] = j < ISAL_HIP_CRC64_RAG_NSQ ? isal_hip_crc64_mulmod(variant, sq[j - 1], sq[j - 1])
+                                                   : ring_one(variant);
+        pw[0] = ring_one(variant);
+        for (j = 1; j <= tt; j++)
+                pw[j] = isal_hip_crc64_mulmod(variant, pw[j - 1], sq[0]);
+}
+
 void
 isal_hip_crc64_geometry(long long len, int tt, isal_hip_crc64_geom *g)
 {

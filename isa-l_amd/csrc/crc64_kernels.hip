@@ -340,6 +340,265 @@ __global__ __launch_bounds__(kBlock) void crc64_combine(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Ragged: stripe s has its own shard length lens[s] (isal_hip_internal.h
+// "ragged CRC64"). The pass is crc64_shards_pre's body with the length, the
+// tile range and the full-tile count read per work item: work item w is row
+// w / nsh of the {stripe, block} item table and shard w % nsh of that stripe,
+// and a workgroup interleaves the chains of items 2v and 2v + 1. The two may
+// differ in their tile counts (another stripe's block, a last block with no
+// full tile), and the last workgroup of an odd count has one: the loop runs
+// to the longer range and skips what an item does not have. Shards are
+// 16-byte aligned by contract; a shard's buffer descriptor is bounded by its
+// own length and only full tiles are loaded. (7 waves per SIMD as
+// crc64_shards_pre: left alone the compiler takes 81 VGPRs, 5 waves; held to
+// 72 it spills nothing.)
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock, 7) void crc64_shards_rag(const uint64_t* __restrict__ ptrs, int nsh,
+                                                           const int* __restrict__ lens,
+                                                           const unsigned* __restrict__ items, unsigned nwork,
+                                                           unsigned tt, int uswap,
+                                                           const uint64_t* __restrict__ image,
+                                                           uint64_t* __restrict__ part) {
+  constexpr int NI = kPreItems, B = kPreBatch;
+  __shared__ uint64_t lt[2 * kCE];  // F_u, F'_u
+  load_lds<2 * kCE>(lt, image + ISAL_HIP_CRC64_RAG_PRE);
+  __syncthreads();
+  const long long lane = threadIdx.x * kVec;
+  auto step = [&](unsigned t, unsigned t1, X64 b, const uint4& x) __attribute__((always_inline)) {
+    X64 c{0u, 0u};
+    if (t + 1 == t1)
+      chunk_acc(c, lt, x.x ^ b.lo, x.y ^ b.hi, x.z, x.w);
+    else
+      chunk_acc(c, lt + kCE, x.x ^ b.lo, x.y ^ b.hi, x.z, x.w);
+    return c;
+  };
+  for (unsigned v = blockIdx.x; NI * v < nwork; v += gridDim.x) {
+    uint64_t base[NI];
+    unsigned t0[NI], t1[NI], n = 0;
+    int len[NI];
+    X64 bc[NI];
+#pragma unroll
+    for (int q = 0; q < NI; ++q) {
+      const unsigned w = NI * v + q;
+      base[q] = 0;
+      t0[q] = t1[q] = 0;
+      len[q] = 0;
+      if (w < nwork) {
+        const unsigned item = w / nsh, i = w - item * nsh;
+        const unsigned stripe = items[2 * static_cast<size_t>(item)], blk = items[2 * static_cast<size_t>(item) + 1];
+        len[q] = lens[stripe];
+        base[q] = ptrs[static_cast<size_t>(stripe) * nsh + i];
+        const unsigned nfull = static_cast<unsigned>(len[q]) / kTile;  // blk * tt <= nfull: the block exists
+        t0[q] = blk * tt;
+        t1[q] = t0[q] + tt < nfull ? t0[q] + tt : nfull;
+      }
+      n = max(n, t1[q] - t0[q]);
+      bc[q] = X64{0u, 0u};
+    }
+    // B tiles of each item in flight, the two chains interleaved step by
+    // step. A tile past an item's own range is neither loaded (its descriptor
+    // is empty) nor stepped: wave-uniform tests, scalar branches.
+    for (unsigned i = 0; i < n; i += B) {
+      uint4 x[NI][B];
+#pragma unroll
+      for (int g = 0; g < B; ++g)
+#pragma unroll
+        for (int q = 0; q < NI; ++q)
+          x[q][g] = load16<kBufNT>(base[q], static_cast<long long>(t0[q] + i + g) * kTile + lane,
+                                   t0[q] + i + g < t1[q] ? len[q] : 0);
+#pragma unroll
+      for (int g = 0; g < B; ++g)
+#pragma unroll
+        for (int q = 0; q < NI; ++q)
+          if (t0[q] + i + g < t1[q]) bc[q] = step(t0[q] + i + g, t1[q], bc[q], x[q][g]);
+    }
+#pragma unroll
+    for (int q = 0; q < NI; ++q) {
+      const unsigned w = NI * v + q;
+      if (w < nwork) {
+        const uint64_t r = bc[q].get();
+        part[static_cast<size_t>(w) * kBlock + threadIdx.x] = uswap ? __builtin_bswap64(r) : r;
+      }
+    }
+  }
+}
+
+// a * b in the flavour's quotient ring (crc64_host.c isal_hip_crc64_mulmod):
+// b is multiplied by x once per coefficient of a, lowest first; the
+// coefficient of x^0 is bit 63 of a refl register and bit 0 of a norm one.
+// 64 shift-and-XOR steps on register pairs, eight VALU ops each: the
+// coefficient's mask is one signed bit-field extract of a (a itself is not
+// shifted), each conditional XOR one three-input bit op per half. (Written on
+// uint64_t the same loop compiled to 64-bit shifts and ran the combine at
+// 0.61-0.69 ms of a 3.4 ms call, profiles/ragged_crc64_kernel_times.jsonl.)
+template <bool REFL>
+__device__ __forceinline__ uint64_t crc64_mulmod(uint64_t a, uint64_t b, uint64_t poly) {
+  const uint32_t ql = static_cast<uint32_t>(poly), qh = static_cast<uint32_t>(poly >> 32);
+  uint32_t bl = static_cast<uint32_t>(b), bh = static_cast<uint32_t>(b >> 32), pl = 0, ph = 0;
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    // the dword of a with the coefficients of x^(32 half) .. x^(32 half + 31)
+    const uint32_t w = static_cast<uint32_t>((half == 0) == REFL ? a >> 32 : a);
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+      const int bit = REFL ? 31 - i : i;
+      const uint32_t ma = static_cast<uint32_t>(static_cast<int32_t>(w << (31 - bit)) >> 31);
+      pl = xor_and(pl, bl, ma);
+      ph = xor_and(ph, bh, ma);
+      if constexpr (REFL) {
+        const uint32_t mb = 0u - (bl & 1u);
+        bl = (bl >> 1) | (bh << 31);
+        bh >>= 1;
+        bl = xor_and(bl, ql, mb);
+        bh = xor_and(bh, qh, mb);
+      } else {
+        const uint32_t mb = static_cast<uint32_t>(static_cast<int32_t>(bh) >> 31);
+        bh = (bh << 1) | (bl >> 31);
+        bl <<= 1;
+        bl = xor_and(bl, ql, mb);
+        bh = xor_and(bh, qh, mb);
+      }
+    }
+  }
+  return (static_cast<uint64_t>(ph) << 32) | pl;
+}
+
+__device__ __forceinline__ uint64_t shfl64(uint64_t v, unsigned src) {
+  const uint32_t lo = __shfl(static_cast<uint32_t>(v), src, 64);
+  const uint32_t hi = __shfl(static_cast<uint32_t>(v >> 32), src, 64);
+  return (static_cast<uint64_t>(hi) << 32) | lo;
+}
+
+// The products of a wave's factors (every lane holds one; 1 where it has
+// none) in five butterfly steps, one crc64_mulmod each: lanes 0..31 form ONE
+// product, which every one of them ends up holding; lanes 32..63 skip the last
+// two steps, so each group of eight there keeps the product of its own eight.
+template <bool REFL>
+__device__ __forceinline__ uint64_t wave_products64(uint64_t v, unsigned lane, uint64_t poly) {
+#pragma unroll 1
+  for (int m = 1; m <= 16; m <<= 1) {
+    const uint32_t lo = __shfl_xor(static_cast<uint32_t>(v), m, 64);
+    const uint32_t hi = __shfl_xor(static_cast<uint32_t>(v >> 32), m, 64);
+    const uint64_t r = crc64_mulmod<REFL>(v, (static_cast<uint64_t>(hi) << 32) | lo, poly);
+    if (m < 8 || lane < 32) v = r;
+  }
+  return v;
+}
+
+// Ragged combine: crc64_combine with every per-length map replaced by a
+// product with a ring element of the length-independent image (crc64_host.c
+// isal_hip_crc64_ragged_image). One wave per shard of len = 4096 nfull + 16 q
+// + rem bytes:
+//  V = Horner over all but the shard's last block with the field tables of
+//      Z^(4096*tt), P = the last block's chains (nfull_last <= tt full tiles),
+//      T = raw(0, the tail's whole chunks), read from the shard (16-byte
+//      aligned, below lens[s]) and right-aligned over the lane positions: each
+//      through wave_fold;
+//  raw(0, all but the last rem bytes) = V * PW[nfull_last] * X[16q] ^ P * X[16q] ^ T
+//      and the register's term ~init * x^(8*len), x^(8*len) = X[len % 4096] *
+//      SQ[i] over the set bits i of nfull, are three products whose factors
+//      lie in different lanes of ONE wave_products64: five multiplications per
+//      shard (the first form ran them one after another, 4 per lane for the
+//      last block, 5 for x^(8*len), 3 in lane 0);
+//  then the last rem bytes one at a time, and crc64 = ~(register term ^ s).
+// A shard of length 0 is init.
+template <bool REFL>
+__global__ __launch_bounds__(kBlock) void crc64_combine_rag(
+    const uint64_t* __restrict__ part, const uint64_t* __restrict__ ptrs, const uint64_t* __restrict__ image,
+    const int* __restrict__ lens, const unsigned* __restrict__ first, unsigned nsh, unsigned tt, uint64_t poly,
+    uint64_t init, uint64_t* __restrict__ out, unsigned nshards) {
+  constexpr unsigned kWaves = kBlock / 64;
+  constexpr uint64_t kOne = REFL ? 1ull << 63 : 1ull;
+  constexpr unsigned kLaneX = ISAL_HIP_CRC64_RAG_NSQ, kLaneInit = kLaneX + 1;  // after the SQ lanes
+  constexpr unsigned kLaneV = 32, kLaneP = 40;                                  // their own groups of eight
+  static_assert(kLaneInit < 32, "the register term's factors fill lanes 0..31");
+  __shared__ uint64_t lt[ISAL_HIP_CRC64_RAG_COMBINE_ENTRIES];
+  load_lds<ISAL_HIP_CRC64_RAG_COMBINE_ENTRIES>(lt, image);
+  __syncthreads();
+  const unsigned lane = threadIdx.x & 63;
+  const uint64_t* tree = lt + ISAL_HIP_CRC64_RAG_TREE;
+  const uint64_t* __restrict__ X = image + ISAL_HIP_CRC64_RAG_X;
+  const uint64_t sq = image[ISAL_HIP_CRC64_RAG_SQ + (lane & 31)];
+  for (unsigned sh = blockIdx.x * kWaves + (threadIdx.x >> 6); sh < nshards; sh += gridDim.x * kWaves) {
+    const unsigned stripe = sh / nsh, i = sh - stripe * nsh;
+    const unsigned len = static_cast<unsigned>(lens[stripe]);
+    if (len == 0) {  // wave-uniform
+      if (lane == 0) out[sh] = init;
+      continue;
+    }
+    const uint64_t base = ptrs[sh];
+    const unsigned nfull = len / kTile, tail = len % kTile;
+    const unsigned q = tail / kVec, rem = tail % kVec;
+    unsigned nfull_last = 0;
+    uint64_t xv = 0, xp = 0, tq = 0;  // V, P, T (lane 0)
+    if (nfull) {                      // wave-uniform
+      const unsigned ntiles = nfull + (tail ? 1u : 0u), nblk = (ntiles + tt - 1) / tt;
+      const unsigned done = (nblk - 1) * tt;  // tiles before the last block
+      nfull_last = nfull > done ? nfull - done : 0u;
+      const uint64_t* pp = part + (static_cast<size_t>(first[stripe]) * nsh + i) * kBlock + 4 * lane;
+      const size_t bstride = static_cast<size_t>(nsh) * kBlock;
+      auto load4 = [&](unsigned b, uint64_t (&p)[4]) __attribute__((always_inline)) {
+        const uint4* p4 = reinterpret_cast<const uint4*>(pp + b * bstride);
+        const uint4 a = p4[0], c = p4[1];
+        p[0] = (static_cast<uint64_t>(a.y) << 32) | a.x;
+        p[1] = (static_cast<uint64_t>(a.w) << 32) | a.z;
+        p[2] = (static_cast<uint64_t>(c.y) << 32) | c.x;
+        p[3] = (static_cast<uint64_t>(c.w) << 32) | c.z;
+      };
+      uint64_t p[4];
+      if (nblk > 1) {  // wave-uniform
+        uint64_t v[4] = {0, 0, 0, 0};
+        for (unsigned b = 0; b + 1 < nblk; ++b) {
+          load4(b, p);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] = apply_op(lt + ISAL_HIP_CRC64_RAG_BLOCK, v[j]) ^ p[j];
+        }
+        xv = wave_fold(tree, v);
+      }
+      load4(nblk - 1, p);
+      xp = wave_fold(tree, p);
+    }
+    if (q) {  // wave-uniform
+      uint64_t v[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = static_cast<int>(4 * lane) + j - (kBlock - static_cast<int>(q));  // tail chunk at this position
+        v[j] = 0;
+        if (c >= 0) {
+          const uint4 w = load16<kPlain>(base, static_cast<long long>(nfull) * kTile + static_cast<long long>(c) * kVec);
+          v[j] = chunk_crc(lt + ISAL_HIP_CRC64_RAG_CHUNK, w.x, w.y, w.z, w.w);
+        }
+      }
+      tq = wave_fold(tree, v);
+    }
+    // this lane's factor (the shuffles by every lane: their source is lane 0)
+    const uint64_t x16q = X[kVec * q];  // wave-uniform (X[0] = 1)
+    const uint64_t bv = shfl64(xv, 0), bp = shfl64(xp, 0);
+    uint64_t f = kOne;
+    if (lane < kLaneX) f = ((nfull >> lane) & 1u) ? sq : kOne;
+    if (lane == kLaneX) f = X[tail];
+    if (lane == kLaneInit) f = ~init;
+    if (lane == kLaneV) f = bv;
+    if (lane == kLaneV + 1) f = image[ISAL_HIP_CRC64_RAG_PW + nfull_last];
+    if (lane == kLaneV + 2 || lane == kLaneP + 1) f = x16q;
+    if (lane == kLaneP) f = bp;
+    f = wave_products64<REFL>(f, lane, poly);
+    const uint64_t sv = shfl64(f, kLaneV), sp = shfl64(f, kLaneP);
+    if (lane == 0) {
+      uint64_t s = sv ^ sp ^ tq;
+      const uint8_t* p = reinterpret_cast<const uint8_t*>(base) + (len - rem);
+      for (unsigned j = 0; j < rem; ++j) {
+        if constexpr (REFL)
+          s = lt[ISAL_HIP_CRC64_RAG_BYTE + ((s ^ p[j]) & 0xff)] ^ (s >> 8);
+        else
+          s = lt[ISAL_HIP_CRC64_RAG_BYTE + (((s >> 56) ^ p[j]) & 0xff)] ^ (s << 8);
+      }
+      out[sh] = ~(f ^ s);
+    }
+  }
+}
+
 constexpr unsigned long long kMaxItems = 1ull << 30;
 
 #else  // ISAL_FUSED64_PART: one object per parity-row count P (parallel build)
@@ -858,6 +1117,44 @@ extern "C" int isal_hip_launch_encode_crc64(const uint64_t* d_ptrs, int k, int r
     if (r) return r;
   }
   return 0;
+}
+
+extern "C" int isal_hip_launch_crc64_ragged(const uint64_t* d_ptrs, int nsh, const int* d_lens,
+                                            const unsigned* d_items, unsigned nitems, int tt, int refl,
+                                            const uint64_t* d_image, uint64_t* d_part, void* stream) {
+  if (nitems == 0 || nsh <= 0) return 0;
+  const unsigned long long nwork = static_cast<unsigned long long>(nitems) * static_cast<unsigned>(nsh);
+  if (nwork > kMaxItems || tt < 1) return static_cast<int>(hipErrorInvalidValue);
+  ISAL_LAUNCH(crc64_shards_rag, dim3(static_cast<unsigned>((nwork + kPreItems - 1) / kPreItems)), dim3(kBlock), 0,
+              static_cast<hipStream_t>(stream), d_ptrs, nsh, d_lens, d_items, static_cast<unsigned>(nwork),
+              static_cast<unsigned>(tt), !refl, d_image, d_part);
+  isal_hip_count_launch();
+  return static_cast<int>(hipGetLastError());
+}
+
+extern "C" int isal_hip_launch_crc64_combine_ragged(const uint64_t* d_part, const uint64_t* d_ptrs,
+                                                    const uint64_t* d_image, const int* d_lens,
+                                                    const unsigned* d_first, int nsh, int tt, int refl,
+                                                    uint64_t poly, uint64_t init, uint64_t* out,
+                                                    long long nstripes, void* stream) {
+  if (nstripes <= 0 || nsh <= 0) return 0;
+  const unsigned long long nshards = static_cast<unsigned long long>(nstripes) * static_cast<unsigned>(nsh);
+  if (nshards > 0xFFFFFFFFull || tt < 1) return static_cast<int>(hipErrorInvalidValue);
+  // four shards per workgroup at a time; each workgroup copies its 41 KB of
+  // tables once, so the grid is capped at what is resident (3 per CU)
+  const unsigned long long want = (nshards + 3) / 4;
+  const unsigned grid = want < 768 ? static_cast<unsigned>(want) : 768u;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (refl)
+    ISAL_LAUNCH(crc64_combine_rag<true>, dim3(grid), dim3(kBlock), 0, s, d_part, d_ptrs, d_image, d_lens, d_first,
+                static_cast<unsigned>(nsh), static_cast<unsigned>(tt), poly, init, out,
+                static_cast<unsigned>(nshards));
+  else
+    ISAL_LAUNCH(crc64_combine_rag<false>, dim3(grid), dim3(kBlock), 0, s, d_part, d_ptrs, d_image, d_lens, d_first,
+                static_cast<unsigned>(nsh), static_cast<unsigned>(tt), poly, init, out,
+                static_cast<unsigned>(nshards));
+  isal_hip_count_launch();
+  return static_cast<int>(hipGetLastError());
 }
 
 #endif  // !ISAL_FUSED64_PART

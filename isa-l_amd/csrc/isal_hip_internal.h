@@ -543,6 +543,14 @@ struct isal_hip_ragged {
         unsigned crc_nitems;
         uint32_t *d_crc, *d_part, *d_tail;
         unsigned *d_crc_items, *d_crc_first;
+        /* CRC64's own (isal_hip_ragged_crc64.c): block size, item tables and
+         * partials from its first call, one image per variant from the first
+         * call with that variant */
+        int c64_tt;
+        unsigned c64_nitems;
+        uint64_t *d_c64part;
+        unsigned *d_c64_items, *d_c64_first;
+        uint64_t *d_c64image[8]; /* ISAL_HIP_CRC64_NVARIANTS */
 };
 /* isal_hip_ragged_encode's body, for a caller already on the object's device */
 int isal_hip_ragged_encode_on_device(struct isal_hip_ragged *r, void *stream);
@@ -558,6 +566,67 @@ int isal_hip_launch_crc_ragged(const uint64_t *d_ptrs, int nsh, const int *d_len
 int isal_hip_launch_crc_combine_ragged(const uint32_t *d_part, const uint32_t *d_tail, const uint32_t *d_image,
                                        const int *d_lens, const unsigned *d_first, int nsh, int tt,
                                        unsigned int init, uint32_t *out, long long nstripes, void *stream);
+
+/* ---- ragged CRC64 (isal_hip_ragged_crc64; crc64_kernels.hip crc64_shards_rag,
+ * crc64_combine_rag) ----------------------------------------------------------
+ * The geometry is the ragged CRC32C's: tt tiles per block, one value per
+ * object; stripe s has ceil(ceil(lens[s]/4096)/tt) blocks, listed as {stripe,
+ * block} by isal_hip_ragged_items(nstripes, lens, 4096*tt), and first[s] is
+ * the row of stripe s's block 0. As in the uniform CRC64 the pass covers the
+ * FULL tiles only: work item (row w, shard i < nsh) leaves
+ *   part[(w * nsh + i) * 256 + L]   the chain of lane L over the block's full
+ *                                   tiles (0 for a last block without one)
+ * and the combine reads the bytes after the last full tile from the shard.
+ * The uniform batch applies Z^(4096*nfull_last), Z^(16*(tail/16)) and Z^len as
+ * maps tabulated on the host for one length; here they are products in the
+ * flavour's quotient ring (crc64_host.c isal_hip_crc64_mulmod; on the device a
+ * 64-step shift-and-XOR) of elements that depend on no length. The image
+ * (isal_hip_crc64_ragged_image, uint64 entries) depends on (variant, tt) alone:
+ *   RAG_BYTE   reference byte table (the last len % 16 bytes)
+ *   RAG_CHUNK  raw(0, 16-byte chunk)                     (the tail's chunks)
+ *   RAG_BLOCK  field tables of Z^(4096*tt)               (Horner across blocks)
+ *   RAG_TREE   Z^(16 * 2^s), s = 0..7                    (wave_fold)
+ *   (crc64_combine_rag keeps BYTE..TREE in LDS: RAG_COMBINE_ENTRIES)
+ *   RAG_PRE    F_u, F'_u of the pre-shifted chains       (all the pass reads)
+ *   RAG_X      X[n] = x^(8n), n < 4096: X[16 * q] shifts the full tiles past the
+ *              tail's chunks, X[len % 4096] is the low part of x^(8*len). (Every
+ *              index is below one tile: the CRC32C image needs two for its
+ *              per-lane W[L]; here wave_fold moves the lanes.)
+ *   RAG_SQ     x^(8*4096*2^i), i < 19, then 1s up to 32  (x^(8*len) by a wave
+ *                                                         product over the set bits of nfull)
+ *   RAG_PW     x^(8*4096*j), j = 0..tt                   (the last block's full tiles)
+ * No Z^4096 table (SHIFT_TAB): only the byte-load kernel of unaligned shards
+ * steps with it, and a ragged batch's shards are 16-byte aligned. */
+#define ISAL_HIP_CRC64_RAG_BYTE 0
+#define ISAL_HIP_CRC64_RAG_CHUNK 256
+#define ISAL_HIP_CRC64_RAG_BLOCK (ISAL_HIP_CRC64_RAG_CHUNK + ISAL_HIP_CRC64_CHUNK_ENTRIES)
+#define ISAL_HIP_CRC64_RAG_TREE (ISAL_HIP_CRC64_RAG_BLOCK + ISAL_HIP_CRC64_OP_ENTRIES)
+#define ISAL_HIP_CRC64_RAG_COMBINE_ENTRIES (ISAL_HIP_CRC64_RAG_TREE + 8 * ISAL_HIP_CRC64_OP_ENTRIES)
+#define ISAL_HIP_CRC64_RAG_PRE ISAL_HIP_CRC64_RAG_COMBINE_ENTRIES
+#define ISAL_HIP_CRC64_RAG_X (ISAL_HIP_CRC64_RAG_PRE + 2 * ISAL_HIP_CRC64_CHUNK_ENTRIES)
+#define ISAL_HIP_CRC64_RAG_X_ENTRIES ISAL_HIP_CRC_TILE
+#define ISAL_HIP_CRC64_RAG_SQ (ISAL_HIP_CRC64_RAG_X + ISAL_HIP_CRC64_RAG_X_ENTRIES)
+#define ISAL_HIP_CRC64_RAG_NSQ 19
+#define ISAL_HIP_CRC64_RAG_SQ_ENTRIES 32 /* a wave's lanes read entry lane % 32 */
+#define ISAL_HIP_CRC64_RAG_PW (ISAL_HIP_CRC64_RAG_SQ + ISAL_HIP_CRC64_RAG_SQ_ENTRIES)
+size_t isal_hip_crc64_ragged_image_entries(int tt);
+void isal_hip_crc64_ragged_image(int variant, int tt, uint64_t *out);
+/* a * b and x^(8n) in the variant's quotient ring, registers in the variant's
+ * bit order; ring_poly: P(x) without x^64 in that order */
+uint64_t isal_hip_crc64_mulmod(int variant, uint64_t a, uint64_t b);
+uint64_t isal_hip_crc64_xpow8n(int variant, unsigned long long n);
+uint64_t isal_hip_crc64_ring_poly(int variant);
+/* One launch over nitems * nsh work items (at most ISAL_HIP_RAGGED_MAX_ITEMS:
+ * hipErrorInvalidValue past it, nothing enqueued); nothing when nitems == 0. */
+int isal_hip_launch_crc64_ragged(const uint64_t *d_ptrs, int nsh, const int *d_lens, const unsigned *d_items,
+                                 unsigned nitems, int tt, int refl, const uint64_t *d_image, uint64_t *d_part,
+                                 void *stream);
+/* out[stripe * nsh + i] = crc64_<variant>(init, shard, lens[stripe]); init for
+ * a stripe of length 0. poly = isal_hip_crc64_ring_poly(variant). One launch. */
+int isal_hip_launch_crc64_combine_ragged(const uint64_t *d_part, const uint64_t *d_ptrs, const uint64_t *d_image,
+                                         const int *d_lens, const unsigned *d_first, int nsh, int tt, int refl,
+                                         uint64_t poly, uint64_t init, uint64_t *out, long long nstripes,
+                                         void *stream);
 
 /* Tiles per CRC workgroup (CRC32C and CRC64) of a launch over nstripes
  * stripes of len-byte shards: def, halved for small launches;

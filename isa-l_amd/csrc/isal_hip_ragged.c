@@ -188,6 +188,12 @@ isal_hip_ragged_destroy(isal_hip_ragged *r)
         isal_hip_obj_drop(r->d_part);
         isal_hip_obj_drop(r->d_crc_items);
         isal_hip_obj_drop(r->d_crc_first);
+        /* ... and the first CRC64 calls (isal_hip_ragged_crc64.c) */
+        isal_hip_obj_drop(r->d_c64part);
+        isal_hip_obj_drop(r->d_c64_items);
+        isal_hip_obj_drop(r->d_c64_first);
+        for (t = 0; t < (int) (sizeof(r->d_c64image) / sizeof(r->d_c64image[0])); t++)
+                isal_hip_obj_drop(r->d_c64image[t]);
         free(r->h_lens);
         isal_hip_obj_drop(r->d_ptrs);
         isal_hip_obj_drop(r->d_tbl);

@@ -139,6 +139,9 @@ def lib() -> ctypes.CDLL:
             "isal_hip_ragged_check": (i, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
             "isal_hip_ragged_crc": (i, [ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]),
             "isal_hip_ragged_encode_crc": (i, [ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]),
+            "isal_hip_ragged_crc64": (i, [ctypes.c_void_p, i, ctypes.c_ulonglong, ctypes.c_void_p, ctypes.c_void_p]),
+            "isal_hip_ragged_encode_crc64": (i, [ctypes.c_void_p, i, ctypes.c_ulonglong, ctypes.c_void_p,
+                                                 ctypes.c_void_p]),
             "isal_hip_ragged_destroy": (i, [ctypes.c_void_p]),
             "isal_hip_pipe_create": (i, [ctypes.POINTER(ctypes.c_void_p), i, i, i, _u8p, i, i]),
             "isal_hip_pipe_submit": (i, [ctypes.c_void_p, _u8pp, _u8pp]),
@@ -680,8 +683,8 @@ class Ragged:
     ragged batch).
 
     data[s*k + j] / coding[s*rows + l] are addresses (or tensors) of 16-byte
-    aligned device buffers, as for Batch. encode(), check(), crc() and
-    encode_crc() only enqueue on `stream`; check() fills the DEVICE buffer bad
+    aligned device buffers, as for Batch. encode(), check(), crc(),
+    encode_crc(), crc64() and encode_crc64() only enqueue on `stream`; check() fills the DEVICE buffer bad
     (one uint64 per stripe) as Batch.check does, ~0 for a stripe of length 0."""
 
     def __init__(self, k: int, rows: int, gftbls, lens: Sequence[int], data: Sequence, coding: Sequence):
@@ -724,6 +727,24 @@ class Ragged:
                                               ctypes.c_void_p(stream))
         if rc != 0:
             raise RuntimeError(f"isal_hip_ragged_encode_crc failed ({rc})")
+
+    def crc64(self, variant: int, init: int, crc, stream: int = 0) -> None:
+        """crc64_<variant>(init, shard, lens[s]) of every source and parity
+        shard into the DEVICE buffer crc (nstripes*(k+rows) uint64, layout as
+        crc()); variant: CRC64_VARIANTS.index(name), as for Batch.crc64. A
+        stripe of length 0 yields init."""
+        rc = lib().isal_hip_ragged_crc64(self._h, variant, init & 0xFFFFFFFFFFFFFFFF, ctypes.c_void_p(addr(crc)),
+                                         ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_ragged_crc64 failed ({rc})")
+
+    def encode_crc64(self, variant: int, init: int, crc, stream: int = 0) -> None:
+        """encode(), then crc64() of the sources and the fresh parity on the
+        same stream (not fused: the encode's launches plus the checksum's)."""
+        rc = lib().isal_hip_ragged_encode_crc64(self._h, variant, init & 0xFFFFFFFFFFFFFFFF,
+                                                ctypes.c_void_p(addr(crc)), ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_ragged_encode_crc64 failed ({rc})")
 
     def close(self) -> None:
         if getattr(self, "_h", None):
