@@ -12,6 +12,7 @@
 // the last < 16 bytes knows the shift direction (REFL).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -963,10 +964,15 @@ void launch_fused64(unsigned grid, hipStream_t s, const uint64_t* ptrs, int ptr_
   const int ragged = g.tail != 0;
   const size_t lds = static_cast<size_t>(k) * kBlock * 8;
 #define FUSED64_LAUNCH(X0, SL, NV)                                                                 \
-  ISAL_LAUNCH((ec_encode_crc64_v16<P, U, X0, SL, NV>), dim3((grid + NV - 1) / NV),           \
-                     dim3(kBlock * NV), lds * NV, s, ptrs, ptr_stride, tbl, len, k, nitems,         \
-                     static_cast<unsigned>(g.nblk), static_cast<unsigned>(g.tt),                    \
-                     static_cast<unsigned>(g.nfull), ragged, xr.src[0], !refl, tabs, part)
+  do {                                                                                             \
+    if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2)                                                     \
+      fprintf(stderr, "isal_hip: kernel ec_encode_crc64_v16<%d, %d, %d, %d, %d>\n", P, U, int(X0), \
+              SL, NV);                                                                             \
+    ISAL_LAUNCH((ec_encode_crc64_v16<P, U, X0, SL, NV>), dim3((grid + NV - 1) / NV),               \
+                dim3(kBlock * NV), lds * NV, s, ptrs, ptr_stride, tbl, len, k, nitems,             \
+                static_cast<unsigned>(g.nblk), static_cast<unsigned>(g.tt),                        \
+                static_cast<unsigned>(g.nfull), ragged, xr.src[0], !refl, tabs, part);             \
+  } while (0)
 #define FUSED64_X0(SL, NV)                                                                        \
   do {                                                                                            \
     if (xr.rows & 1u) FUSED64_LAUNCH(true, SL, NV); else FUSED64_LAUNCH(false, SL, NV);           \

@@ -19,6 +19,7 @@
 //    block XOR-reduction, then adds Z^len(init_crc).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -833,12 +834,17 @@ void launch_fused(unsigned grid, size_t lds, hipStream_t s, const uint64_t* ptrs
                   const isal_hip_crc_geom& g, const isal_hip_xrows& xr, const uint32_t* tabs,
                   uint32_t* part, uint32_t* tail, int nshard_total, int crc_src, int out_shard0) {
 #define FUSED_LAUNCH(REG, SRC, X0, LDS, NB, NV)                                                  \
-  ISAL_LAUNCH((ec_encode_crc_v16<P, FusedPol<U>, REG, SRC, X0, NB, NV>),                   \
-                     dim3((grid + NV - 1) / NV), dim3(kBlock * NV), (LDS) * NV, s, ptrs, ptr_stride, \
-                     src0, dst0, tbl, len, k, nitems, static_cast<unsigned>(g.nblk),               \
-                     static_cast<unsigned>(g.tt), static_cast<unsigned>(g.nfull),                  \
-                     static_cast<unsigned>(g.ntiles), xr.src[0], tabs, part, tail, nshard_total,   \
-                     out_shard0, 0)
+  do {                                                                                           \
+    if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2)                                                   \
+      fprintf(stderr, "isal_hip: kernel ec_encode_crc_v16<%d, %d, %d, %d, %d, %d>\n", P, U,      \
+              int(SRC), int(X0), NB, NV);                                                        \
+    ISAL_LAUNCH((ec_encode_crc_v16<P, FusedPol<U>, REG, SRC, X0, NB, NV>),                       \
+                dim3((grid + NV - 1) / NV), dim3(kBlock * NV), (LDS) * NV, s, ptrs, ptr_stride,  \
+                src0, dst0, tbl, len, k, nitems, static_cast<unsigned>(g.nblk),                  \
+                static_cast<unsigned>(g.tt), static_cast<unsigned>(g.nfull),                     \
+                static_cast<unsigned>(g.ntiles), xr.src[0], tabs, part, tail, nshard_total,      \
+                out_shard0, 0);                                                                  \
+  } while (0)
   const bool x0 = crc_src && (xr.rows & 1u);
   const bool nv2 = crc_src && fused_nv32(k) == 2;
   if (!crc_src)
