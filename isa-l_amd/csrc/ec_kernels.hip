@@ -1151,6 +1151,7 @@ void encode_pass(const uint64_t* ptrs, int ptr_stride, int src0, int dst0, const
       launch_v16<P, decltype(u)::value>(s, ptrs, ptr_stride, src0, dst0, tbl, len, k, nstripes, x, r0m, c0m);
     });
   } else {
+    if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2) fprintf(stderr, "isal_hip: kernel ec_encode_b1<%d>\n", P);
     ISAL_LAUNCH(ec_encode_b1<P>, dim3(grid), dim3(kBlock), 0, s, ptrs, ptr_stride, src0,
                        dst0, tbl, len, k, nitems, tiles);
   }
@@ -1173,6 +1174,12 @@ void update_pass(const uint64_t* ptrs, int ptr_stride, int src_idx, int dst0, co
   const unsigned nitems = nstripes * tiles;
   // (An occupancy cap through dynamic LDS measured flat at 8 workgroups per
   // CU and 2-9 % slower at 4-6, profiles/r04_update_occupancy_ab.jsonl.)
+  if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2) {
+    if (vec16)
+      fprintf(stderr, "isal_hip: kernel ec_update_v16<%d, %d>\n", P, kUpdBlock);
+    else
+      fprintf(stderr, "isal_hip: kernel ec_update_b1<%d>\n", P);
+  }
   if (vec16)
     ISAL_LAUNCH((ec_update_v16<P, kUpdBlock>), dim3(grid_for(nitems)), dim3(kUpdBlock), 0, s, ptrs, ptr_stride,
                 src_idx, dst0, tbl, len, nitems, tiles);
@@ -1857,6 +1864,10 @@ extern "C" int isal_hip_launch_encode_karg(const isal_hip_karg* a, const isal_hi
   const bool launched = with_rows(rows, [&](auto P) {
     with_enc_group(k, 0, [&](auto u) {
       with_xor(m.x, [&](auto fl) {
+        // the instantiation behind the line above: its load group and 0/1 form
+        if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2)
+          fprintf(stderr, "isal_hip: kernel ec_encode_karg<%d, EncPol<%d, %d, %d, %d>, %d>\n", decltype(P)::value,
+                  decltype(u)::value, kBufNT, kBufSC1NT, 2, decltype(fl)::value);
         ISAL_LAUNCH((ec_encode_karg<decltype(P)::value, EncPol<decltype(u)::value, kBufNT, kBufSC1NT, 2>,
                                     decltype(fl)::value>),
                     dim3(tiles), dim3(kBlock), 0, s, *a, *d, len, k, tiles, m.r0m, m.c0m);
@@ -1875,6 +1886,7 @@ extern "C" int isal_hip_launch_update_karg(const isal_hip_karg* a, const isal_hi
   if (rows > EC_MAX_ROWS_PER_PASS) return static_cast<int>(hipErrorInvalidValue);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const unsigned tiles = tiles_of(len, kTile);
+  if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2) fprintf(stderr, "isal_hip: kernel ec_update_karg<%d>\n", rows);
   with_rows(rows, [&](auto P) {
     ISAL_LAUNCH(ec_update_karg<decltype(P)::value>, dim3(tiles), dim3(kBlock), 0, s, *a, *d, len, tiles);
   });
@@ -1934,6 +1946,8 @@ extern "C" int isal_hip_launch_verify(const uint64_t* d_ptrs, int ptr_stride, in
     unsigned long long* out = slots + *nslots;
     if (!vec16) {
       with_rows(p.P, [&](auto P) {
+        if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2)
+          fprintf(stderr, "isal_hip: kernel ec_verify_b1<%d>\n", decltype(P)::value);
         ISAL_LAUNCH(ec_verify_b1<decltype(P)::value>, dim3(grid), dim3(kBlock), 0, s, d_ptrs, ptr_stride, src_idx0,
                     dst_idx0 + p.r0, p.tbl, len, k, tiles, tiles, out, p.r0, col0);
       });
@@ -2108,6 +2122,9 @@ extern "C" int isal_hip_launch_verify_karg(const isal_hip_karg* a, const isal_hi
   const unsigned tiles = tiles_of(len, kTile);
   const PassMask m = pass_mask(em, 0);
   if (!with_verify_case(rows, k, m.x, [&](auto P, auto U, auto FL) {
+        if (isal_hip_knob(ISAL_HIP_KNOB_LOG) >= 2)
+          fprintf(stderr, "isal_hip: kernel ec_verify_karg<%d, %d, %d>\n", decltype(P)::value, decltype(U)::value,
+                  decltype(FL)::value);
         ISAL_LAUNCH(
             (ec_verify_karg<decltype(P)::value, EncPol<decltype(U)::value, kBufNT, kBufNT, 0>, decltype(FL)::value>),
             dim3(tiles), dim3(kBlock), 0, s, *a, *d, len, k, tiles, m.r0m, m.c0m);

@@ -38,21 +38,24 @@ EXPECTED = {"ec_repair_v16": 48, "ec_encode_rag": 48, "ec_repair_rag": 48, "ec_v
             "ec_verify_v16": 64, "ec_locate_v16": 56, "ec_overwrite_v16": 16}
 
 
-def built_cells(kernels):
+def built_cells(kernels, mangled=None, cell=None):
     """family -> [(cell, policy tail)] for every kernel name of the families,
     cell as CELLS spells it. A name of a family that the pattern does not
-    match is an error: it would be an instantiation this module cannot see."""
-    out = {f: [] for f in MANGLED}
+    match is an error: it would be an instantiation this module cannot see.
+    mangled and cell: another matrix's families (test_encode_matrix_cpu.py)
+    in place of this module's MANGLED and CELL."""
+    mangled, cell = mangled or MANGLED, cell or CELL
+    out = {f: [] for f in mangled}
     for name in sorted(kernels):
-        for family, args in MANGLED.items():
+        for family, args in mangled.items():
             m = re.search(rf"\d+{family}I", name)
             if not m:
                 continue
             m = re.search(rf"{len(family)}{family}{args}Ev", name)
             assert m, f"{name}: template arguments of {family} not understood"
             g = [int(x) for x in m.groups()]
-            out[family].append((tuple(g[i] for i in CELL[family]), tuple(x for i, x in enumerate(g)
-                                                                       if i not in CELL[family])))
+            out[family].append((tuple(g[i] for i in cell[family]), tuple(x for i, x in enumerate(g)
+                                                                       if i not in cell[family])))
     return out
 
 

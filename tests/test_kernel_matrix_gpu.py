@@ -26,6 +26,14 @@ verify and locate kernels take their group from verify_group, which does not
 read ISAL_HIP_ENC_GROUP, so the k = 20 cell exists for the encode-like families
 only; ec_overwrite_v16 has no load group over k, so it has no remainder cells.
 
+The encode family itself is covered elsewhere: the batch encode and update
+kernels (ec_encode_v16, ec_encode_glds, ec_encode_ldsx, ec_encode_b1,
+ec_update_v16, ec_update_b1) and the drop-in kernels on device shards
+(ec_encode_karg, ec_encode_karg4, ec_encode_karg_ldsx, ec_update_karg,
+ec_verify_karg, ec_verify_b1) have their own matrix of the same build in
+tests/test_encode_matrix_{cpu,gpu}.py, and the fused encode + checksum kernels
+in tests/test_fused_crc_matrix_{cpu,gpu}.py.
+
 Each cell proves which kernel ran: under ISAL_HIP_LOG=2 the library's
 `isal_hip: kernel NAME<...>` lines must name exactly the cell's instantiation,
 and kernel_launches() must grow by the expected count.
@@ -137,7 +145,9 @@ def _name(family, cell):
 
 class Launches:
     """What one step of a cell launched: the kernel lines of the log and the
-    growth of kernel_launches() must both say `count` launches of `name`."""
+    growth of kernel_launches() must both say `count` launches of `name`.
+    `name` may also be the list of the step's kernel lines, in order, where
+    they differ (passes of different widths, test_encode_matrix_gpu.py)."""
 
     def __init__(self, engine, capfd, name):
         self.engine, self.capfd, self.name = engine, capfd, name
@@ -151,7 +161,8 @@ class Launches:
         grew = self.engine.kernel_launches() - before
         err = self.capfd.readouterr().err
         named = [line.split("kernel ", 1)[1] for line in err.splitlines() if line.startswith("isal_hip: kernel ")]
-        assert named == [self.name] * count, (self.name, named)
+        want = [self.name] * count if isinstance(self.name, str) else list(self.name)
+        assert named == want, (self.name, named)
         assert grew == count, (self.name, grew)
         return out
 
