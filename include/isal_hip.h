@@ -655,6 +655,70 @@ int isal_hip_ragged_encode_crc64(isal_hip_ragged *r, int variant, unsigned long 
                                  unsigned long long *crc, void *stream);
 int isal_hip_ragged_destroy(isal_hip_ragged *r);
 
+/* ---- sector checksums: one word per 512 B .. 4 KiB of every shard --------- */
+
+/*
+ * Where the entry points above checksum whole shards (what Ceph's EC hash info
+ * stores), these keep ONE WORD PER FIXED-SIZE SECTOR of every shard: HDFS
+ * striped block groups (CRC32C per 512-byte bytesPerChecksum chunk), BlueStore
+ * (CRC32C per 4 KiB csum block), NVMe end-to-end protection (a guard per 512 B
+ * or 4 KiB logical block; its 64-bit guard is ISAL_HIP_CRC64_ROCKSOFT_REFL).
+ * After a scrub has named a shard they also say which sector of it to rebuild.
+ *
+ * sector is a power of two, 512 <= sector <= 4096. A shard of len bytes has
+ * ns = ceil(len / sector) sectors; sector i covers bytes [i*sector,
+ * min((i+1)*sector, len)): the last one may be short, down to 1 byte, and a
+ * shard of length 0 has none. Each sector's word is what the reference
+ * function returns for those bytes alone, with the same init for every sector:
+ *   crc32_iscsi(p, n, init)        (the register starts at init, no inversion)
+ *   crc64_<variant>(init, p, n)    (starts at ~init, inverted on return)
+ * crc is a DEVICE array; with m = k + rows and shard j of a stripe its source
+ * j (j < k) or its parity row j - k:
+ *   isal_hip_batch_sector_crc, _crc64    crc[(s*m + j)*ns + i]
+ *   isal_hip_ragged_sector_crc, _crc64   crc[m*first[s] + j*ns_s + i], ns_s =
+ *       ceil(lens[s] / sector), first[s] = the sum of ns_t over t < s
+ * isal_hip_ragged_sector_offsets: pure arithmetic, no GPU: fills first[0 ..
+ *   nstripes) (first may be NULL) and returns the sum over all stripes, so crc
+ *   holds m times the returned count; -1 for arguments outside the contract
+ *   (NULL lens, nstripes <= 0, a negative length, a bad sector).
+ * The four launch functions:
+ *   ISAL_HIP_EINVAL, with nothing enqueued and no HIP call (so a host without a
+ *   GPU answers the same), for a NULL object or crc, a sector that is not one
+ *   of 512, 1024, 2048, 4096, a variant outside [0, ISAL_HIP_CRC64_NVARIANTS),
+ *   on the uniform batch any shard not 16-byte aligned (isal_hip_batch_check's
+ *   rule), and more than 2^30 work items (4 KiB tiles of every shard) in the
+ *   launch, which is refused, not sliced.
+ *   A call only enqueues, on the caller's stream and the object's device,
+ *   whatever the calling thread's current device: exactly ONE kernel launch
+ *   (isal_hip_kernel_launches grows by 1), no combine launch and no partials
+ *   in global memory, because a sector never leaves a 4 KiB tile. With len ==
+ *   0, or every ragged length 0, it returns 0, enqueues nothing and leaves crc
+ *   untouched. Idempotent: every word of every sector is rewritten by each
+ *   call, nothing is written past the last word or to the shards, and nothing
+ *   is read at or past a shard's own length.
+ *   Memory, freed by the object's destroy: the first call with a flavour
+ *   uploads that flavour's tables (9.6 KiB for CRC32C, 31.5 KiB per crc64
+ *   variant), which depend on the flavour only, never on a length or on
+ *   sector; the first ragged call with a sector size uploads first[] for it (8
+ *   bytes per stripe); the ragged work items are the encode's 4 KiB {stripe,
+ *   tile} table. A failed allocation returns ISAL_HIP_ENOMEM or ISAL_HIP_EHIP,
+ *   leaves no HIP error behind and the object as usable as before.
+ * Out of scope: sectors below 512 B or above one 4 KiB tile; CRC16 T10-DIF,
+ * the 16-bit NVMe guard (a new polynomial's tables and the rest of crc.h: the
+ * natural follow-up); fusing into the encode pass; comparing against stored
+ * checksums on the device; unaligned or host-pageable shards; any CPU route;
+ * the drop-in ABI.
+ */
+int isal_hip_batch_sector_crc(isal_hip_batch *b, int sector, unsigned int init, unsigned int *crc,
+                              void *stream);
+int isal_hip_batch_sector_crc64(isal_hip_batch *b, int variant, int sector, unsigned long long init,
+                                unsigned long long *crc, void *stream);
+long long isal_hip_ragged_sector_offsets(int nstripes, const int *lens, int sector, long long *first);
+int isal_hip_ragged_sector_crc(isal_hip_ragged *r, int sector, unsigned int init, unsigned int *crc,
+                               void *stream);
+int isal_hip_ragged_sector_crc64(isal_hip_ragged *r, int variant, int sector, unsigned long long init,
+                                 unsigned long long *crc, void *stream);
+
 /* ---- streaming pipeline for HOST-resident stripes ----------------------- */
 
 /*

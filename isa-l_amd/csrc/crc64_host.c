@@ -311,6 +311,27 @@ isal_hip_crc64_tables(int variant, long long len, int tt, uint64_t *tabs)
         }
 }
 
+/* The sector checksums' image (ISAL_HIP_SECTOR64_ENTRIES, isal_hip_internal.h
+ * "sector checksums"): the chunk map as above, then Z^(16 * 2^s) as OP_TREE
+ * holds them, one more (Z^1024) and none of the length-dependent maps. */
+void
+isal_hip_crc64_sector_image(int variant, uint64_t *out)
+{
+        uint64_t basis[128], m[64];
+        uint8_t chunk[16];
+        int j, s;
+        for (j = 0; j < 128; j++) {
+                memset(chunk, 0, sizeof(chunk));
+                chunk[j / 8] = (uint8_t) (1u << (j % 8));
+                basis[j] = raw_update(variant, 0, chunk, 16);
+        }
+        chunk_tables(basis, out);
+        for (s = 0; s < ISAL_HIP_SECTOR_NZ; s++) {
+                isal_hip_crc64_zpow(variant, 16ULL << s, m);
+                op_tables(m, out + ISAL_HIP_CRC64_CHUNK_ENTRIES + s * ISAL_HIP_CRC64_OP_ENTRIES);
+        }
+}
+
 /* Tables of the CPU route (crc_cpu.c): the reference's byte table and the
  * slicing-by-8 tables A_j[v] = pi(raw(0, v at byte j of 8)) (the u-domain step
  * of slice_tables above, without the pre-shifted half). */

@@ -130,6 +130,26 @@ isal_hip_crc32c_tables(uint32_t *tabs)
                 }
 }
 
+/* The sector checksums' image (ISAL_HIP_SECTOR32_DWORDS, isal_hip_internal.h
+ * "sector checksums"): the chunk field tables above, then the field tables of
+ * Z^(16 * 2^d) in the layout of SHIFT_TAB. */
+void
+isal_hip_crc32c_sector_image(uint32_t *out)
+{
+        uint32_t tabs[ISAL_HIP_CRC_TAB_DWORDS];
+        int d, f, v;
+        isal_hip_crc32c_tables(tabs);
+        memcpy(out, tabs + ISAL_HIP_CRC_CHUNK_TAB, ISAL_HIP_CRC_CHUNK_DWORDS * sizeof(uint32_t));
+        out += ISAL_HIP_CRC_CHUNK_DWORDS;
+        for (d = 0; d < ISAL_HIP_SECTOR_NZ; d++) {
+                const uint32_t z = isal_hip_crc32c_xpow8n(16ULL << d);
+                for (f = 0; f < ISAL_HIP_CRC_FIELDS; f++)
+                        for (v = 0; v < 32; v++)
+                                out[(d * ISAL_HIP_CRC_FIELDS + f) * 32 + v] = isal_hip_crc32c_mulmod(
+                                        (uint32_t) (v & ((1 << field_bits(f)) - 1)) << field_lo(f), z);
+        }
+}
+
 /* Byte-position tables (ISAL_HIP_CRC_B16_TAB): out[p * 256 + b] = crc of byte
  * b followed by 15 - p zero bytes, then the same shifted by 4080 more zero
  * bytes (multiplied by x^(8*4080) mod P, as the chain shift tables are). */

@@ -14,26 +14,9 @@
 #include "isal_hip.h"
 #include "isal_hip_internal.h"
 
-struct isal_hip_batch {
-        int len, k, rows, nstripes, device, vec16;
-        uint64_t *d_ptrs;
-        uint32_t *d_tbl;
-        isal_hip_xrows xr; /* 0/1 parity rows: CRCs derived, not computed */
-        isal_hip_encmask em; /* 0/1 rows and columns: XORs instead of lookups */
-        /* CRC32C state, allocated on first use: kernel tables + combine plan,
-         * and the per-lane partials (crc_kernels.hip) */
-        uint64_t *d_ldsx; /* LDS product tables of the wide passes (NULL: not used) */
-        isal_hip_crc_geom crc;
-        uint32_t *d_crc, *d_part, *d_tail;
-        /* CRC64 state, allocated on first use: one table set per variant
-         * and pass used (never overwritten, so switching variants needs no
-         * device synchronisation) and the per-lane chains. The fused pass
-         * (c64_tt tiles per block) and the checksum-only pass (c64_tt_ck)
-         * have their own block geometry; the partials are sized for the
-         * shorter blocks. */
-        int c64_tt, c64_tt_ck;
-        uint64_t *d_c64tab[ISAL_HIP_CRC64_NVARIANTS], *d_c64tab_ck[ISAL_HIP_CRC64_NVARIANTS], *d_c64part;
-};
+_Static_assert(sizeof(((isal_hip_batch *) 0)->d_c64tab) / sizeof(uint64_t *) == ISAL_HIP_CRC64_NVARIANTS &&
+                       sizeof(((isal_hip_batch *) 0)->d_sec64) / sizeof(uint64_t *) == ISAL_HIP_CRC64_NVARIANTS,
+               "one table slot per variant (struct isal_hip_batch, isal_hip_internal.h)");
 
 /* Every shard of a batch on device dev: hipMalloc memory of dev, managed
  * memory, or page-locked host memory whose device address is its host address.
@@ -274,6 +257,10 @@ isal_hip_batch_destroy(isal_hip_batch *b)
         }
         if (b->d_c64part)
                 (void) hipFree(b->d_c64part);
+        /* what the sector checksums uploaded (isal_hip_sector_crc.c) */
+        isal_hip_obj_drop(b->d_sec32);
+        for (int v = 0; v < ISAL_HIP_CRC64_NVARIANTS; v++)
+                isal_hip_obj_drop(b->d_sec64[v]);
         free(b);
         return ISAL_HIP_OK;
 }

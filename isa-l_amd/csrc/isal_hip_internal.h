@@ -551,6 +551,12 @@ struct isal_hip_ragged {
         uint64_t *d_c64part;
         unsigned *d_c64_items, *d_c64_first;
         uint64_t *d_c64image[8]; /* ISAL_HIP_CRC64_NVARIANTS */
+        /* the sector checksums' own (isal_hip_sector_crc.c): one image per
+         * flavour and one table of first sectors per sector size, each from the
+         * first call that needs it */
+        uint32_t *d_sec32;
+        uint64_t *d_sec64[8];
+        unsigned long long *d_sec_first[4]; /* ISAL_HIP_SECTOR_NSIZES */
 };
 /* isal_hip_ragged_encode's body, for a caller already on the object's device */
 int isal_hip_ragged_encode_on_device(struct isal_hip_ragged *r, void *stream);
@@ -733,6 +739,77 @@ int isal_hip_launch_encode_crc(const uint64_t *d_ptrs, int ptr_stride, int src_i
 int isal_hip_launch_crc_combine(const uint32_t *d_part, const uint32_t *d_tail,
                                 const uint32_t *d_plan, long long nblk, int has_tail,
                                 unsigned int init, uint32_t *out, long long nsh, void *stream);
+
+/* ---- sector checksums (isal_hip_sector_crc.c, crc_sector_kernels.hip) -------
+ * One word per `sector` bytes of every shard (isal_hip.h "sector checksums"),
+ * sector a power of two from ISAL_HIP_SECTOR_MIN to one CRC tile. The device
+ * images depend on the flavour alone, never on a length or the sector size:
+ *   CRC32C (dwords)   the chunk map, ISAL_HIP_CRC_CHUNK_DWORDS (the layout of
+ *                     CHUNK_TAB), then the field tables (the layout of
+ *                     SHIFT_TAB) of Z^(16 * 2^d), d = 0 .. ISAL_HIP_SECTOR_NZ - 1
+ *   crc64 (entries)   the chunk map, ISAL_HIP_CRC64_CHUNK_ENTRIES, then the 14
+ *                     field tables of the same seven maps
+ * Z^16 .. Z^512 join the lanes of a wave, Z^1024 the waves of a 2 or 4 KiB
+ * sector. */
+#define ISAL_HIP_SECTOR_MIN 512
+#define ISAL_HIP_SECTOR_NZ 7
+#define ISAL_HIP_SECTOR_NSIZES 4 /* 512, 1024, 2048, 4096 */
+#define ISAL_HIP_SECTOR32_DWORDS (ISAL_HIP_CRC_CHUNK_DWORDS + ISAL_HIP_SECTOR_NZ * ISAL_HIP_CRC_FIELDS * 32)
+#define ISAL_HIP_SECTOR64_ENTRIES (ISAL_HIP_CRC64_CHUNK_ENTRIES + ISAL_HIP_SECTOR_NZ * ISAL_HIP_CRC64_OP_ENTRIES)
+void isal_hip_crc32c_sector_image(uint32_t *out);
+void isal_hip_crc64_sector_image(int variant, uint64_t *out);
+/* Where the nwork (shard, 4 KiB tile) work items of a launch lie. d_ptrs: rows
+ * of nsh shard addresses, every one 16-byte aligned. Uniform (d_items NULL):
+ * every shard has len bytes in ntiles tiles, item w is tile w % ntiles of shard
+ * w / ntiles, whose sector 0 is word (w / ntiles) * ceil(len / sector). Ragged:
+ * item w is shard w % nsh of row w / nsh of the {stripe, tile} table d_items
+ * (ISAL_HIP_RAGGED_TILE-byte tiles), the stripe's length is d_lens[stripe] and
+ * sector 0 of its shard j is word nsh * d_first[stripe] + j * ceil(len / sector)
+ * (d_first: isal_hip_ragged_sector_offsets). */
+typedef struct {
+        const uint64_t *d_ptrs;
+        int nsh, sector;
+        unsigned long long nwork;
+        int len;
+        unsigned ntiles;
+        const int *d_lens;
+        const unsigned *d_items;
+        const unsigned long long *d_first;
+} isal_hip_sector_geom;
+/* One launch, no other: out[word] = crc32_iscsi(sector bytes, n, init) /
+ * crc64 of the flavour whose image, direction and ring polynomial
+ * (isal_hip_crc64_ring_poly) are given. hipErrorInvalidValue, nothing
+ * enqueued, for nwork == 0 or past ISAL_HIP_RAGGED_MAX_ITEMS or a bad sector. */
+int isal_hip_launch_sector_crc32c(const isal_hip_sector_geom *g, const uint32_t *d_image, unsigned int init,
+                                  uint32_t *out, void *stream);
+int isal_hip_launch_sector_crc64(const isal_hip_sector_geom *g, const uint64_t *d_image, int refl, uint64_t poly,
+                                 uint64_t init, uint64_t *out, void *stream);
+
+/* The uniform batch object (isal_hip_batch.c; its sector checksums are
+ * isal_hip_sector_crc.c's). */
+struct isal_hip_batch {
+        int len, k, rows, nstripes, device, vec16;
+        uint64_t *d_ptrs;
+        uint32_t *d_tbl;
+        isal_hip_xrows xr; /* 0/1 parity rows: CRCs derived, not computed */
+        isal_hip_encmask em; /* 0/1 rows and columns: XORs instead of lookups */
+        /* CRC32C state, allocated on first use: kernel tables + combine plan,
+         * and the per-lane partials (crc_kernels.hip) */
+        uint64_t *d_ldsx; /* LDS product tables of the wide passes (NULL: not used) */
+        isal_hip_crc_geom crc;
+        uint32_t *d_crc, *d_part, *d_tail;
+        /* CRC64 state, allocated on first use: one table set per variant
+         * and pass used (never overwritten, so switching variants needs no
+         * device synchronisation) and the per-lane chains. The fused pass
+         * (c64_tt tiles per block) and the checksum-only pass (c64_tt_ck)
+         * have their own block geometry; the partials are sized for the
+         * shorter blocks. */
+        int c64_tt, c64_tt_ck;
+        uint64_t *d_c64tab[8], *d_c64tab_ck[8], *d_c64part; /* ISAL_HIP_CRC64_NVARIANTS */
+        /* the sector checksums' images, from the first call that needs one */
+        uint32_t *d_sec32;
+        uint64_t *d_sec64[8];
+};
 
 #ifdef __cplusplus
 }

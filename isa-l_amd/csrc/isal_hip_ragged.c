@@ -194,6 +194,12 @@ isal_hip_ragged_destroy(isal_hip_ragged *r)
         isal_hip_obj_drop(r->d_c64_first);
         for (t = 0; t < (int) (sizeof(r->d_c64image) / sizeof(r->d_c64image[0])); t++)
                 isal_hip_obj_drop(r->d_c64image[t]);
+        /* ... and the sector checksums (isal_hip_sector_crc.c) */
+        isal_hip_obj_drop(r->d_sec32);
+        for (t = 0; t < (int) (sizeof(r->d_sec64) / sizeof(r->d_sec64[0])); t++)
+                isal_hip_obj_drop(r->d_sec64[t]);
+        for (t = 0; t < ISAL_HIP_SECTOR_NSIZES; t++)
+                isal_hip_obj_drop(r->d_sec_first[t]);
         free(r->h_lens);
         isal_hip_obj_drop(r->d_ptrs);
         isal_hip_obj_drop(r->d_tbl);

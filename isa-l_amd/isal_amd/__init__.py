@@ -27,7 +27,7 @@ __all__ = [
     "ec_encode_data_base", "ec_encode_data_update", "ec_encode_data_update_base",
     "gf_vect_dot_prod", "gf_vect_dot_prod_base", "gf_vect_mad", "gf_vect_mad_base",
     "gf_vect_mul", "gf_vect_mul_base", "Batch", "Repair", "decode_matrix", "ESINGULAR", "Scrub", "scrub_ambiguity",
-    "locate_syndrome", "SCRUB_CLEAN", "SCRUB_MULTI", "Ragged", "ragged_items", "Pipe", "kernel_launches", "max_rows_per_pass",
+    "locate_syndrome", "SCRUB_CLEAN", "SCRUB_MULTI", "Ragged", "ragged_items", "ragged_sector_offsets", "Pipe", "kernel_launches", "max_rows_per_pass",
     "version", "addr", "cpu_calls", "fallbacks", "reload_config", "Multi", "partition",
     "route_device", "contexts_created", "selftest_kernels", "crc32_iscsi", "crc64", "CRC64_VARIANTS", "slow_waits",
 ]
@@ -143,6 +143,14 @@ def lib() -> ctypes.CDLL:
             "isal_hip_ragged_encode_crc64": (i, [ctypes.c_void_p, i, ctypes.c_ulonglong, ctypes.c_void_p,
                                                  ctypes.c_void_p]),
             "isal_hip_ragged_destroy": (i, [ctypes.c_void_p]),
+            "isal_hip_batch_sector_crc": (i, [ctypes.c_void_p, i, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]),
+            "isal_hip_batch_sector_crc64": (i, [ctypes.c_void_p, i, i, ctypes.c_ulonglong, ctypes.c_void_p,
+                                                ctypes.c_void_p]),
+            "isal_hip_ragged_sector_offsets": (ctypes.c_longlong, [i, ctypes.POINTER(ctypes.c_int), i,
+                                                                   ctypes.POINTER(ctypes.c_longlong)]),
+            "isal_hip_ragged_sector_crc": (i, [ctypes.c_void_p, i, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]),
+            "isal_hip_ragged_sector_crc64": (i, [ctypes.c_void_p, i, i, ctypes.c_ulonglong, ctypes.c_void_p,
+                                                 ctypes.c_void_p]),
             "isal_hip_pipe_create": (i, [ctypes.POINTER(ctypes.c_void_p), i, i, i, _u8p, i, i]),
             "isal_hip_pipe_submit": (i, [ctypes.c_void_p, _u8pp, _u8pp]),
             "isal_hip_pipe_flush": (i, [ctypes.c_void_p]),
@@ -387,6 +395,25 @@ class Batch:
                                                ctypes.c_void_p(addr(crc)), ctypes.c_void_p(stream))
         if rc != 0:
             raise RuntimeError(f"isal_hip_batch_encode_crc64 failed ({rc})")
+
+    def sector_crc(self, sector: int, init: int, crc, stream: int = 0) -> None:
+        """crc32_iscsi(sector bytes, n, init) of every `sector` bytes (512, 1024,
+        2048 or 4096; the last sector of a shard may be short) of every shard
+        into the DEVICE buffer crc: nstripes*(k+rows)*ns uint32 with ns =
+        ceil(len / sector), word (s*(k+rows) + j)*ns + i for sector i of shard
+        j of stripe s. One launch (isal_hip_batch_sector_crc)."""
+        rc = lib().isal_hip_batch_sector_crc(self._h, sector, init & 0xFFFFFFFF, ctypes.c_void_p(addr(crc)),
+                                             ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_batch_sector_crc failed ({rc})")
+
+    def sector_crc64(self, variant: int, sector: int, init: int, crc, stream: int = 0) -> None:
+        """crc64_<variant>(init, sector bytes, n) of every sector, 64-bit words
+        laid out as sector_crc()'s; variant as for crc64()."""
+        rc = lib().isal_hip_batch_sector_crc64(self._h, variant, sector, init & 0xFFFFFFFFFFFFFFFF,
+                                               ctypes.c_void_p(addr(crc)), ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_batch_sector_crc64 failed ({rc})")
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -677,6 +704,19 @@ def ragged_items(lens: Sequence[int], tile: int) -> np.ndarray:
     return items
 
 
+def ragged_sector_offsets(lens: Sequence[int], sector: int) -> tuple[np.ndarray, int]:
+    """isal_hip_ragged_sector_offsets (host arithmetic, no GPU): first[s], the
+    number of sectors of one shard of the stripes before s (int64), and the
+    total over all stripes; Ragged.sector_crc writes (k+rows) * total words."""
+    ln = np.array(list(lens), dtype=np.int32)
+    first = np.zeros(ln.size, dtype=np.int64)
+    total = int(lib().isal_hip_ragged_sector_offsets(int(ln.size), ln.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                     sector, first.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))))
+    if total < 0:
+        raise ValueError("lens must be non-empty and non-negative, sector one of 512, 1024, 2048, 4096")
+    return first, total
+
+
 class Ragged:
     """len(lens) stripes of one geometry, stripe s with shards of lens[s]
     bytes, encoded or checked by one launch per pass (include/isal_hip.h
@@ -745,6 +785,26 @@ class Ragged:
                                                 ctypes.c_void_p(addr(crc)), ctypes.c_void_p(stream))
         if rc != 0:
             raise RuntimeError(f"isal_hip_ragged_encode_crc64 failed ({rc})")
+
+    def sector_crc(self, sector: int, init: int, crc, stream: int = 0) -> None:
+        """crc32_iscsi(sector bytes, n, init) of every `sector` bytes (512, 1024,
+        2048 or 4096) of every shard into the DEVICE buffer crc ((k+rows) *
+        total uint32): with (first, total) = ragged_sector_offsets(lens,
+        sector) and ns = ceil(lens[s] / sector), sector i of shard j of stripe
+        s is word (k+rows)*first[s] + j*ns + i. One launch
+        (isal_hip_ragged_sector_crc); nothing when every length is 0."""
+        rc = lib().isal_hip_ragged_sector_crc(self._h, sector, init & 0xFFFFFFFF, ctypes.c_void_p(addr(crc)),
+                                              ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_ragged_sector_crc failed ({rc})")
+
+    def sector_crc64(self, variant: int, sector: int, init: int, crc, stream: int = 0) -> None:
+        """crc64_<variant>(init, sector bytes, n) of every sector, 64-bit words
+        laid out as sector_crc()'s; variant as for crc64()."""
+        rc = lib().isal_hip_ragged_sector_crc64(self._h, variant, sector, init & 0xFFFFFFFFFFFFFFFF,
+                                                ctypes.c_void_p(addr(crc)), ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(f"isal_hip_ragged_sector_crc64 failed ({rc})")
 
     def close(self) -> None:
         if getattr(self, "_h", None):
