@@ -18,115 +18,22 @@
 
 #include <type_traits>
 
-#include "ec_device.h"
+#include "crc_device.h"
 
 namespace {
 
-constexpr int kF = ISAL_HIP_CRC_FIELDS;
 [[maybe_unused]] constexpr int kOp = ISAL_HIP_CRC64_OP_ENTRIES;
 [[maybe_unused]] constexpr int kKernTab = ISAL_HIP_CRC64_OP_BLOCK - ISAL_HIP_CRC64_CHUNK_TAB;  // chunk + shift
 [[maybe_unused]] constexpr int kChunk = 0;                                                        // offsets in LDS copy
 [[maybe_unused]] constexpr int kShift = ISAL_HIP_CRC64_SHIFT_TAB - ISAL_HIP_CRC64_CHUNK_TAB;
 
-static_assert(ISAL_HIP_CRC_TILE == kTile, "CRC tile = encode tile");
-static_assert(kF == 7, "field layout below assumes 7 fields per dword");
-
-template <int OFF, int WIDTH>
-__device__ __forceinline__ uint32_t bfe(uint32_t x) {
-  uint32_t r;
-  asm("v_bfe_u32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "n"(OFF), "n"(WIDTH));
-  return r;
-}
-
-// Byte offsets (entry index * 8) of the 7 fields of w, bits [0,5) [5,10)
-// [10,15) [15,20) [20,25) [25,30) [30,32). w << 3 puts fields 0-4 at their
-// entry offsets; the even and odd fields are masked into separate words so
-// that one bit-field extract per field lands on zeros below it. Fields 5 and 6
-// would leave the dword after the shift and come from w directly.
-__device__ __forceinline__ void field_offsets8(uint32_t w, uint32_t (&o)[kF]) {
-  const uint32_t s = w << 3;
-  const uint32_t ev = s & 0x0F83E0F8u;  // fields 0, 2, 4 at [3,8) [13,18) [23,28)
-  const uint32_t od = s & 0x007C1F00u;  // fields 1, 3 at [8,13) [18,23)
-  o[0] = ev & 0xF8u;
-  o[1] = bfe<5, 8>(od);
-  o[2] = bfe<10, 8>(ev);
-  o[3] = bfe<15, 8>(od);
-  o[4] = bfe<20, 8>(ev);
-  o[5] = (w >> 22) & 0xF8u;
-  o[6] = (w >> 27) & 0x18u;
-}
-
-// 64-bit XOR accumulator kept as two dwords so that every fold is one
-// v_bitop3 (3-input XOR) per half: a lookup costs one XOR op instead of two
-// (the compiler does not form bitop3 from 64-bit XOR chains by itself).
-struct X64 {
-  uint32_t lo, hi;
-  __device__ __forceinline__ void add2(uint64_t x, uint64_t y) {
-    lo = xor3(lo, static_cast<uint32_t>(x), static_cast<uint32_t>(y));
-    hi = xor3(hi, static_cast<uint32_t>(x >> 32), static_cast<uint32_t>(y >> 32));
-  }
-  __device__ __forceinline__ void add(uint64_t x) {
-    lo ^= static_cast<uint32_t>(x);
-    hi ^= static_cast<uint32_t>(x >> 32);
-  }
-  __device__ __forceinline__ uint64_t get() const {
-    return (static_cast<uint64_t>(hi) << 32) | lo;
-  }
-};
-
-__device__ __forceinline__ __attribute__((unused)) X64 x64(uint64_t v) {
-  return {static_cast<uint32_t>(v), static_cast<uint32_t>(v >> 32)};
-}
-
-// Entry of field f of table set t at byte offset o (field tables are 256 B apart).
-__device__ __forceinline__ uint64_t tab_at(const uint64_t* t, int f, uint32_t o) {
-  return *reinterpret_cast<const uint64_t*>(reinterpret_cast<const char*>(t) + f * 256 + o);
-}
-
-// acc ^= the 14 field lookups of the two dwords (w0, w1) in the 14 consecutive
-// 32-entry tables at t: seven 3-input XORs per half.
-__device__ __forceinline__ void lookup14(X64& acc, const uint64_t* t, uint32_t w0, uint32_t w1) {
-  uint32_t o[kF], q[kF];
-  field_offsets8(w0, o);
-  field_offsets8(w1, q);
-  const uint64_t* u = t + kF * 32;
-  acc.add2(tab_at(t, 0, o[0]), tab_at(t, 1, o[1]));
-  acc.add2(tab_at(t, 2, o[2]), tab_at(t, 3, o[3]));
-  acc.add2(tab_at(t, 4, o[4]), tab_at(t, 5, o[5]));
-  acc.add2(tab_at(t, 6, o[6]), tab_at(u, 0, q[0]));
-  acc.add2(tab_at(u, 1, q[1]), tab_at(u, 2, q[2]));
-  acc.add2(tab_at(u, 3, q[3]), tab_at(u, 4, q[4]));
-  acc.add2(tab_at(u, 5, q[5]), tab_at(u, 6, q[6]));
-}
-
-// acc ^= M(v) for a map stored as 14 field tables.
-__device__ __forceinline__ void apply_op_acc(X64& acc, const uint64_t* op, uint64_t v) {
-  lookup14(acc, op, static_cast<uint32_t>(v), static_cast<uint32_t>(v >> 32));
-}
-
-__device__ __forceinline__ __attribute__((unused)) uint64_t apply_op(const uint64_t* op, uint64_t v) {
-  X64 a{0u, 0u};
-  apply_op_acc(a, op, v);
-  return a.get();
-}
-
-// acc ^= raw(0, 16-byte chunk) through the chunk map at t, dwords little-endian.
-__device__ __forceinline__ void chunk_acc(X64& acc, const uint64_t* t, uint32_t w0, uint32_t w1,
-                                          uint32_t w2, uint32_t w3) {
-  constexpr int D = kF * 32;
-  lookup14(acc, t, w0, w1);
-  lookup14(acc, t + 2 * D, w2, w3);
-}
-
+// raw(0, 16-byte chunk) through the chunk map at t (the field lookups, X64 and
+// the maps built from them are crc_device.h's).
 __device__ __forceinline__ uint64_t chunk_crc(const uint64_t* t, uint32_t w0, uint32_t w1,
                                               uint32_t w2, uint32_t w3) {
   X64 a{0u, 0u};
   chunk_acc(a, t, w0, w1, w2, w3);
   return a.get();
-}
-
-__device__ __forceinline__ uint32_t le32(const uint8_t* p) {
-  return p[0] | (p[1] << 8) | (p[2] << 16) | (static_cast<uint32_t>(p[3]) << 24);
 }
 
 // raw(0, 16 bytes at base + off) with byte loads (any alignment).
@@ -165,7 +72,8 @@ __global__ __launch_bounds__(kBlock) void crc64_shards_bytes(const uint64_t* __r
     const unsigned si = w / nblk, blk = w - si * nblk;
     const unsigned stripe = si / nsh, i = si - stripe * nsh;
     const uint64_t base = ptrs[static_cast<size_t>(stripe) * ptr_stride + i];
-    const unsigned t0 = blk * tt, t1 = t0 + tt < nfull ? t0 + tt : nfull;
+    unsigned t0, t1;
+    block_tiles(blk, tt, nfull, t0, t1);
     uint64_t a = 0;
     for (unsigned t = t0; t < t1; ++t)
       a = apply_op(lt + kShift, a) ^ chunk_crc_bytes(lt + kChunk, base, static_cast<long long>(t) * kTile + lane);
@@ -191,6 +99,44 @@ __global__ __launch_bounds__(kBlock) void crc64_shards_bytes(const uint64_t* __r
 // below (0.650-0.668).
 constexpr int kPreItems = 2, kPreBatch = 4;
 
+// What crc64_shards_pre and crc64_shards_rag share. LDS holds F_u at 0 and
+// F'_u at kCE. One step of a pre-shifted chain b: the chain goes into the
+// chunk's first 8 bytes like a CRC register and the chunk through the map at f,
+// F'_u, or F_u for the item's last tile. (The choice between the two stays in
+// the kernels, where the table is the LDS array itself: taken inside a function
+// that gets the table as a pointer, crc64_shards_pre came out at 98 VGPRs, 4
+// waves per SIMD, instead of 72 and 7.)
+__device__ __forceinline__ X64 pre_map64(const uint64_t* f, X64 b, const uint4& x) {
+  X64 c{0u, 0u};
+  chunk_acc(c, f, x.x ^ b.lo, x.y ^ b.hi, x.z, x.w);
+  return c;
+}
+
+// One of the kPreItems items a workgroup interleaves: the shard, its length (the
+// bound of its buffer descriptor), its full tiles [t0, t1) and its chain. An
+// item past the launch's last stays empty.
+struct PreItem {
+  uint64_t base = 0;
+  int len = 0;
+  unsigned t0 = 0, t1 = 0;
+  X64 b{0u, 0u};
+  // block blk of tt tiles of the shard's nfull full tiles
+  __device__ __forceinline__ void set(uint64_t base_, int len_, unsigned blk, unsigned tt, unsigned nfull) {
+    base = base_;
+    len = len_;
+    block_tiles(blk, tt, nfull, t0, t1);
+  }
+  __device__ __forceinline__ uint4 load(unsigned t, int bound) const {
+    return load16<kBufNT>(base, static_cast<long long>(t) * kTile + threadIdx.x * kVec, bound);
+  }
+  // the lane's chain of work item w, as a register of the flavour (u =
+  // bswap(s) for the norm ones)
+  __device__ __forceinline__ void store(uint64_t* __restrict__ part, unsigned w, int uswap) const {
+    const uint64_t r = b.get();
+    part[static_cast<size_t>(w) * kBlock + threadIdx.x] = uswap ? __builtin_bswap64(r) : r;
+  }
+};
+
 __global__ __launch_bounds__(kBlock) void crc64_shards_pre(const uint64_t* __restrict__ ptrs, int ptr_stride,
                                                            int nsh, int len, unsigned nitems, unsigned nblk,
                                                            unsigned tt, unsigned nfull, int uswap,
@@ -200,56 +146,41 @@ __global__ __launch_bounds__(kBlock) void crc64_shards_pre(const uint64_t* __res
   __shared__ uint64_t lt[2 * kCE];  // F_u, F'_u
   load_lds<2 * kCE>(lt, tabs + ISAL_HIP_CRC64_PRE_TAB);
   __syncthreads();
-  const long long lane = threadIdx.x * kVec;
-  auto step = [&](unsigned t, unsigned t1, X64 b, const uint4& x) __attribute__((always_inline)) {
-    X64 c{0u, 0u};
-    if (t + 1 == t1)
-      chunk_acc(c, lt, x.x ^ b.lo, x.y ^ b.hi, x.z, x.w);
-    else
-      chunk_acc(c, lt + kCE, x.x ^ b.lo, x.y ^ b.hi, x.z, x.w);
-    return c;
+  auto step = [&](PreItem& it, unsigned t, const uint4& x) __attribute__((always_inline)) {
+    it.b = t + 1 == it.t1 ? pre_map64(lt, it.b, x) : pre_map64(lt + kCE, it.b, x);
   };
   for (unsigned v = blockIdx.x; NI * v < nitems; v += gridDim.x) {
-    uint64_t base[NI];
-    unsigned t0[NI], t1[NI], n = ~0u;
-    X64 bc[NI];
+    PreItem it[NI];
+    unsigned n = ~0u;
 #pragma unroll
     for (int q = 0; q < NI; ++q) {
       const unsigned w = NI * v + q;
-      base[q] = 0;
-      t0[q] = t1[q] = 0;
       if (w < nitems) {
         const unsigned si = w / nblk, blk = w - si * nblk;
         const unsigned stripe = si / nsh, i = si - stripe * nsh;
-        base[q] = ptrs[static_cast<size_t>(stripe) * ptr_stride + i];
-        t0[q] = blk * tt;
-        t1[q] = t0[q] + tt < nfull ? t0[q] + tt : nfull;
+        it[q].set(ptrs[static_cast<size_t>(stripe) * ptr_stride + i], len, blk, tt, nfull);
       }
-      n = min(n, t1[q] - t0[q]);
-      bc[q] = X64{0u, 0u};
+      n = min(n, it[q].t1 - it[q].t0);
     }
+    // B tiles of each item together while both have them, the two chains
+    // interleaved step by step; then what is left of each, a tile at a time
     unsigned i = 0;
     for (; i + B <= n; i += B) {
       uint4 x[NI][B];
 #pragma unroll
       for (int g = 0; g < B; ++g)
 #pragma unroll
-        for (int q = 0; q < NI; ++q)
-          x[q][g] = load16<kBufNT>(base[q], static_cast<long long>(t0[q] + i + g) * kTile + lane, len);
+        for (int q = 0; q < NI; ++q) x[q][g] = it[q].load(it[q].t0 + i + g, len);
 #pragma unroll
       for (int g = 0; g < B; ++g)
 #pragma unroll
-        for (int q = 0; q < NI; ++q) bc[q] = step(t0[q] + i + g, t1[q], bc[q], x[q][g]);
+        for (int q = 0; q < NI; ++q) step(it[q], it[q].t0 + i + g, x[q][g]);
     }
 #pragma unroll
     for (int q = 0; q < NI; ++q) {
-      for (unsigned j = t0[q] + i; j < t1[q]; ++j)
-        bc[q] = step(j, t1[q], bc[q], load16<kBufNT>(base[q], static_cast<long long>(j) * kTile + lane, len));
+      for (unsigned j = it[q].t0 + i; j < it[q].t1; ++j) step(it[q], j, it[q].load(j, len));
       const unsigned w = NI * v + q;
-      if (w < nitems) {
-        const uint64_t r = bc[q].get();
-        part[static_cast<size_t>(w) * kBlock + threadIdx.x] = uswap ? __builtin_bswap64(r) : r;
-      }
+      if (w < nitems) it[q].store(part, w, uswap);
     }
   }
 }
@@ -271,6 +202,45 @@ __device__ __forceinline__ uint64_t wave_fold(const uint64_t* tree, const uint64
     h = apply_op(tree + (s + 2) * kOp, h) ^ ((static_cast<uint64_t>(hi) << 32) | lo);
   }
   return h;
+}
+
+// What crc64_combine and crc64_combine_rag share.
+// The partials of a lane's four lane positions (four consecutive words at p).
+__device__ __forceinline__ void load_part4(const uint64_t* p, uint64_t (&v)[4]) {
+  const uint4* p4 = reinterpret_cast<const uint4*>(p);
+  const uint4 a = p4[0], c = p4[1];
+  v[0] = (static_cast<uint64_t>(a.y) << 32) | a.x;
+  v[1] = (static_cast<uint64_t>(a.w) << 32) | a.z;
+  v[2] = (static_cast<uint64_t>(c.y) << 32) | c.x;
+  v[3] = (static_cast<uint64_t>(c.w) << 32) | c.z;
+}
+
+// raw(0, the q whole 16-byte chunks of a shard's tail), in lane 0: the chunks
+// right-aligned over the 256 lane positions, so the last one sits at position
+// 255, then wave_fold. chunk(c) = raw(0, chunk c of the tail): the reader
+// carries its kernel's alignment contract.
+template <class Chunk>
+__device__ __forceinline__ uint64_t tail_fold(const uint64_t* tree, unsigned lane, int q, Chunk&& chunk) {
+  uint64_t v[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int c = static_cast<int>(4 * lane) + j - (kBlock - q);  // tail chunk at this position
+    v[j] = c >= 0 ? chunk(c) : 0;
+  }
+  return wave_fold(tree, v);
+}
+
+// The register s run over the last rem < 16 bytes at p, through the
+// reference's byte table: the one place that knows the shift direction.
+template <bool REFL>
+__device__ __forceinline__ uint64_t tail_bytes(const uint64_t* byte_tab, uint64_t s, const uint8_t* p, int rem) {
+  for (int j = 0; j < rem; ++j) {
+    if constexpr (REFL)
+      s = byte_tab[(s ^ p[j]) & 0xff] ^ (s >> 8);
+    else
+      s = byte_tab[((s >> 56) ^ p[j]) & 0xff] ^ (s << 8);
+  }
+  return s;
 }
 
 // One wave per shard (grid-stride, four shards per workgroup at a time, the
@@ -306,36 +276,22 @@ __global__ __launch_bounds__(kBlock) void crc64_combine(
       uint64_t v[4] = {0, 0, 0, 0};
       for (unsigned b = 0; b < nblk; ++b) {
         const uint64_t* op = lt + (b + 1 == nblk ? ISAL_HIP_CRC64_OP_LAST : ISAL_HIP_CRC64_OP_BLOCK);
-        const uint4* p4 = reinterpret_cast<const uint4*>(pp + static_cast<size_t>(b) * kBlock);
-        const uint4 a = p4[0], c = p4[1];
-        const uint64_t p[4] = {(static_cast<uint64_t>(a.y) << 32) | a.x, (static_cast<uint64_t>(a.w) << 32) | a.z,
-                               (static_cast<uint64_t>(c.y) << 32) | c.x, (static_cast<uint64_t>(c.w) << 32) | c.z};
+        uint64_t p[4];
+        load_part4(pp + static_cast<size_t>(b) * kBlock, p);
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = apply_op(op, v[j]) ^ p[j];
       }
       x = wave_fold(tree, v);
     }
-    if (q) {
-      uint64_t v[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = static_cast<int>(4 * lane) + j - (kBlock - q);  // tail chunk at this position
-        v[j] = c >= 0 ? chunk_crc_bytes(lt + ISAL_HIP_CRC64_CHUNK_TAB, base,
-                                        static_cast<long long>(nfull) * kTile + static_cast<long long>(c) * kVec)
-                      : 0;
-      }
-      tq = wave_fold(tree, v);
-    }
+    if (q)  // byte loads: any alignment
+      tq = tail_fold(tree, lane, q, [&](int c) __attribute__((always_inline)) {
+        return chunk_crc_bytes(lt + ISAL_HIP_CRC64_CHUNK_TAB, base,
+                               static_cast<long long>(nfull) * kTile + static_cast<long long>(c) * kVec);
+      });
     if (lane == 0) {
       uint64_t s = x;
       if (q) s = apply_op(lt + ISAL_HIP_CRC64_OP_TAIL, s) ^ tq;
-      const uint8_t* p = reinterpret_cast<const uint8_t*>(base) + (len - rem);
-      for (int j = 0; j < rem; ++j) {
-        if constexpr (REFL)
-          s = lt[ISAL_HIP_CRC64_BYTE_TAB + ((s ^ p[j]) & 0xff)] ^ (s >> 8);
-        else
-          s = lt[ISAL_HIP_CRC64_BYTE_TAB + (((s >> 56) ^ p[j]) & 0xff)] ^ (s << 8);
-      }
+      s = tail_bytes<REFL>(lt + ISAL_HIP_CRC64_BYTE_TAB, s, reinterpret_cast<const uint8_t*>(base) + (len - rem), rem);
       out[sh] = ~(init_term ^ s);
     }
   }
@@ -343,8 +299,9 @@ __global__ __launch_bounds__(kBlock) void crc64_combine(
 
 // ---------------------------------------------------------------------------
 // Ragged: stripe s has its own shard length lens[s] (isal_hip_internal.h
-// "ragged CRC64"). The pass is crc64_shards_pre's body with the length, the
-// tile range and the full-tile count read per work item: work item w is row
+// "ragged CRC64"). The pass is crc64_shards_pre's, on the same PreItem and
+// pre_map64, with the length, the tile range and the full-tile count read per
+// work item and its own batch loop: work item w is row
 // w / nsh of the {stripe, block} item table and shard w % nsh of that stripe,
 // and a workgroup interleaves the chains of items 2v and 2v + 1. The two may
 // differ in their tile counts (another stripe's block, a last block with no
@@ -365,37 +322,23 @@ __global__ __launch_bounds__(kBlock, 7) void crc64_shards_rag(const uint64_t* __
   __shared__ uint64_t lt[2 * kCE];  // F_u, F'_u
   load_lds<2 * kCE>(lt, image + ISAL_HIP_CRC64_RAG_PRE);
   __syncthreads();
-  const long long lane = threadIdx.x * kVec;
-  auto step = [&](unsigned t, unsigned t1, X64 b, const uint4& x) __attribute__((always_inline)) {
-    X64 c{0u, 0u};
-    if (t + 1 == t1)
-      chunk_acc(c, lt, x.x ^ b.lo, x.y ^ b.hi, x.z, x.w);
-    else
-      chunk_acc(c, lt + kCE, x.x ^ b.lo, x.y ^ b.hi, x.z, x.w);
-    return c;
+  auto step = [&](PreItem& it, unsigned t, const uint4& x) __attribute__((always_inline)) {
+    it.b = t + 1 == it.t1 ? pre_map64(lt, it.b, x) : pre_map64(lt + kCE, it.b, x);
   };
   for (unsigned v = blockIdx.x; NI * v < nwork; v += gridDim.x) {
-    uint64_t base[NI];
-    unsigned t0[NI], t1[NI], n = 0;
-    int len[NI];
-    X64 bc[NI];
+    PreItem it[NI];
+    unsigned n = 0;
 #pragma unroll
     for (int q = 0; q < NI; ++q) {
       const unsigned w = NI * v + q;
-      base[q] = 0;
-      t0[q] = t1[q] = 0;
-      len[q] = 0;
       if (w < nwork) {
         const unsigned item = w / nsh, i = w - item * nsh;
         const unsigned stripe = items[2 * static_cast<size_t>(item)], blk = items[2 * static_cast<size_t>(item) + 1];
-        len[q] = lens[stripe];
-        base[q] = ptrs[static_cast<size_t>(stripe) * nsh + i];
-        const unsigned nfull = static_cast<unsigned>(len[q]) / kTile;  // blk * tt <= nfull: the block exists
-        t0[q] = blk * tt;
-        t1[q] = t0[q] + tt < nfull ? t0[q] + tt : nfull;
+        const int len = lens[stripe];
+        // blk * tt <= nfull: the block exists
+        it[q].set(ptrs[static_cast<size_t>(stripe) * nsh + i], len, blk, tt, static_cast<unsigned>(len) / kTile);
       }
-      n = max(n, t1[q] - t0[q]);
-      bc[q] = X64{0u, 0u};
+      n = max(n, it[q].t1 - it[q].t0);
     }
     // B tiles of each item in flight, the two chains interleaved step by
     // step. A tile past an item's own range is neither loaded (its descriptor
@@ -405,22 +348,20 @@ __global__ __launch_bounds__(kBlock, 7) void crc64_shards_rag(const uint64_t* __
 #pragma unroll
       for (int g = 0; g < B; ++g)
 #pragma unroll
-        for (int q = 0; q < NI; ++q)
-          x[q][g] = load16<kBufNT>(base[q], static_cast<long long>(t0[q] + i + g) * kTile + lane,
-                                   t0[q] + i + g < t1[q] ? len[q] : 0);
+        for (int q = 0; q < NI; ++q) {
+          const unsigned t = it[q].t0 + i + g;
+          x[q][g] = it[q].load(t, t < it[q].t1 ? it[q].len : 0);
+        }
 #pragma unroll
       for (int g = 0; g < B; ++g)
 #pragma unroll
         for (int q = 0; q < NI; ++q)
-          if (t0[q] + i + g < t1[q]) bc[q] = step(t0[q] + i + g, t1[q], bc[q], x[q][g]);
+          if (it[q].t0 + i + g < it[q].t1) step(it[q], it[q].t0 + i + g, x[q][g]);
     }
 #pragma unroll
     for (int q = 0; q < NI; ++q) {
       const unsigned w = NI * v + q;
-      if (w < nwork) {
-        const uint64_t r = bc[q].get();
-        part[static_cast<size_t>(w) * kBlock + threadIdx.x] = uswap ? __builtin_bswap64(r) : r;
-      }
+      if (w < nwork) it[q].store(part, w, uswap);
     }
   }
 }
@@ -539,40 +480,24 @@ __global__ __launch_bounds__(kBlock) void crc64_combine_rag(
       nfull_last = nfull > done ? nfull - done : 0u;
       const uint64_t* pp = part + (static_cast<size_t>(first[stripe]) * nsh + i) * kBlock + 4 * lane;
       const size_t bstride = static_cast<size_t>(nsh) * kBlock;
-      auto load4 = [&](unsigned b, uint64_t (&p)[4]) __attribute__((always_inline)) {
-        const uint4* p4 = reinterpret_cast<const uint4*>(pp + b * bstride);
-        const uint4 a = p4[0], c = p4[1];
-        p[0] = (static_cast<uint64_t>(a.y) << 32) | a.x;
-        p[1] = (static_cast<uint64_t>(a.w) << 32) | a.z;
-        p[2] = (static_cast<uint64_t>(c.y) << 32) | c.x;
-        p[3] = (static_cast<uint64_t>(c.w) << 32) | c.z;
-      };
       uint64_t p[4];
       if (nblk > 1) {  // wave-uniform
         uint64_t v[4] = {0, 0, 0, 0};
         for (unsigned b = 0; b + 1 < nblk; ++b) {
-          load4(b, p);
+          load_part4(pp + b * bstride, p);
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] = apply_op(lt + ISAL_HIP_CRC64_RAG_BLOCK, v[j]) ^ p[j];
         }
         xv = wave_fold(tree, v);
       }
-      load4(nblk - 1, p);
+      load_part4(pp + (nblk - 1) * bstride, p);
       xp = wave_fold(tree, p);
     }
-    if (q) {  // wave-uniform
-      uint64_t v[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = static_cast<int>(4 * lane) + j - (kBlock - static_cast<int>(q));  // tail chunk at this position
-        v[j] = 0;
-        if (c >= 0) {
-          const uint4 w = load16<kPlain>(base, static_cast<long long>(nfull) * kTile + static_cast<long long>(c) * kVec);
-          v[j] = chunk_crc(lt + ISAL_HIP_CRC64_RAG_CHUNK, w.x, w.y, w.z, w.w);
-        }
-      }
-      tq = wave_fold(tree, v);
-    }
+    if (q)  // wave-uniform; 16-byte loads: the shards are aligned by contract
+      tq = tail_fold(tree, lane, static_cast<int>(q), [&](int c) __attribute__((always_inline)) {
+        const uint4 w = load16<kPlain>(base, static_cast<long long>(nfull) * kTile + static_cast<long long>(c) * kVec);
+        return chunk_crc(lt + ISAL_HIP_CRC64_RAG_CHUNK, w.x, w.y, w.z, w.w);
+      });
     // this lane's factor (the shuffles by every lane: their source is lane 0)
     const uint64_t x16q = X[kVec * q];  // wave-uniform (X[0] = 1)
     const uint64_t bv = shfl64(xv, 0), bp = shfl64(xp, 0);
@@ -587,20 +512,12 @@ __global__ __launch_bounds__(kBlock) void crc64_combine_rag(
     f = wave_products64<REFL>(f, lane, poly);
     const uint64_t sv = shfl64(f, kLaneV), sp = shfl64(f, kLaneP);
     if (lane == 0) {
-      uint64_t s = sv ^ sp ^ tq;
-      const uint8_t* p = reinterpret_cast<const uint8_t*>(base) + (len - rem);
-      for (unsigned j = 0; j < rem; ++j) {
-        if constexpr (REFL)
-          s = lt[ISAL_HIP_CRC64_RAG_BYTE + ((s ^ p[j]) & 0xff)] ^ (s >> 8);
-        else
-          s = lt[ISAL_HIP_CRC64_RAG_BYTE + (((s >> 56) ^ p[j]) & 0xff)] ^ (s << 8);
-      }
+      const uint64_t s = tail_bytes<REFL>(lt + ISAL_HIP_CRC64_RAG_BYTE, sv ^ sp ^ tq,
+                                          reinterpret_cast<const uint8_t*>(base) + (len - rem), static_cast<int>(rem));
       out[sh] = ~(f ^ s);
     }
   }
 }
-
-constexpr unsigned long long kMaxItems = 1ull << 30;
 
 #else  // ISAL_FUSED64_PART: one object per parity-row count P (parallel build)
 
@@ -614,39 +531,10 @@ constexpr unsigned long long kMaxItems = 1ull << 30;
 // layout (shards 0..k-1 = sources, k..k+P-1 = parity) and crc64_combine
 // finishes them, reading the ragged tail (len % 4096) straight from the
 // shards: the kernel's last block encodes that tile without checksumming it.
-// Source chains live in LDS (lane-private words).
+// Source chains live in LDS (lane-private words). The fold of a load group with
+// its chain feed (mac_feed) and the group's loads (enc_load_group) are
+// ec_device.h's, shared with the fused CRC32C kernel.
 // ---------------------------------------------------------------------------
-template <int P, int U, bool R0 = false, class Feed>
-__device__ __forceinline__ void mac_feed(uint32_t (&acc)[P][4], const uint4 (&x)[U], int j,
-                                         const uint32_t* __restrict__ tbl, Feed&& feed, unsigned long long x0src = 0) {
-  constexpr int PAIR = P <= 4 ? 2 : 1;
-#pragma unroll
-  for (int u = 0; u + PAIR <= U; u += PAIR) {
-    if constexpr (PAIR == 2) {
-      mac16x2<P, R0>(acc, x[u], x[u + 1], tbl + (j + u) * P * kTbl, tbl + (j + u + 1) * P * kTbl,
-                     r0_mask(x0src, j + u), r0_mask(x0src, j + u + 1));
-      feed(j + u, x[u]);
-      feed(j + u + 1, x[u + 1]);
-    } else {
-      mac16<P, R0>(acc, x[u], tbl + (j + u) * P * kTbl, r0_mask(x0src, j + u));
-      feed(j + u, x[u]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  if constexpr (PAIR == 2 && (U & 1)) {
-    mac16<P, R0>(acc, x[U - 1], tbl + (j + U - 1) * P * kTbl, r0_mask(x0src, j + U - 1));
-    feed(j + U - 1, x[U - 1]);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-template <int U>
-__device__ __forceinline__ void load_grp(uint4 (&x)[U], const uint64_t* __restrict__ sp, int j,
-                                         long long off, int len) {
-#pragma unroll
-  for (int u = 0; u < U; ++u) x[u] = load16<kNT>(sp[j + u], off, len);
-}
-
 // ---- the fused kernel's chunk path: pre-shifted chains, byte tables --------
 // In the u-domain (crc64_host.c: u = pi(s), one update rule u' = A(d ^ u) for
 // every flavour) a lane keeps its chain PRE-SHIFTED: b = Z^4080_u(a), the
@@ -657,7 +545,7 @@ __device__ __forceinline__ void load_grp(uint4 (&x)[U], const uint64_t* __restri
 //   u1 = A(lo8 ^ b),  b' = A'(hi8 ^ u1)   (A' = Z^4080_u o A)
 // and the block's last tile ends with A instead of A', leaving the plain
 // chain a. 16 byte-indexed lookups per chunk, each offset one SDWA shift
-// (byte select + << 3); the 256-entry tables are not bank-conflict-free (8
+// (byte_offs: byte select + << 3); the 256-entry tables are not bank-conflict-free (8
 // entries per bank pair): VALU issue traded for LDS cycles.
 //
 // Formulations measured and removed (profiles/r05/r05_fused_model.txt):
@@ -669,19 +557,6 @@ __device__ __forceinline__ void load_grp(uint4 (&x)[U], const uint64_t* __restri
 constexpr int kSA = 0, kSB = 8 * 256;  // A, A' in LDS
 constexpr int kSlLds = 16 * 256;
 
-// Byte b of w times 8 (an 8-byte entry's offset) in one VALU op.
-__device__ __forceinline__ void byte_offs8(uint32_t w, uint32_t (&o)[4]) {
-  const uint32_t three = 3;
-  asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0"
-      : "=v"(o[0]) : "v"(three), "v"(w));
-  asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1"
-      : "=v"(o[1]) : "v"(three), "v"(w));
-  asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2"
-      : "=v"(o[2]) : "v"(three), "v"(w));
-  asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3"
-      : "=v"(o[3]) : "v"(three), "v"(w));
-}
-
 __device__ __forceinline__ uint64_t tab8_at(const uint64_t* t, int j, uint32_t o) {
   return *reinterpret_cast<const uint64_t*>(reinterpret_cast<const char*>(t) + j * 2048 + o);
 }
@@ -689,8 +564,8 @@ __device__ __forceinline__ uint64_t tab8_at(const uint64_t* t, int j, uint32_t o
 // acc ^= S(lo | hi << 32) for the slicing table set S at t (8 tables of 256).
 __device__ __forceinline__ void slice8_acc(X64& acc, const uint64_t* t, uint32_t lo, uint32_t hi) {
   uint32_t o[4], q[4];
-  byte_offs8(lo, o);
-  byte_offs8(hi, q);
+  byte_offs<3>(lo, o);
+  byte_offs<3>(hi, q);
   acc.add2(tab8_at(t, 0, o[0]), tab8_at(t, 1, o[1]));
   acc.add2(tab8_at(t, 2, o[2]), tab8_at(t, 3, o[3]));
   acc.add2(tab8_at(t, 4, q[0]), tab8_at(t, 5, q[1]));
@@ -738,8 +613,8 @@ __device__ __forceinline__ uint64_t tab8_issue(const uint64_t* t, int j, uint32_
 
 [[maybe_unused]] __device__ __forceinline__ void issue8(Look8& r, const uint64_t* t, uint32_t lo, uint32_t hi) {
   uint32_t o[4], q[4];
-  byte_offs8(lo, o);
-  byte_offs8(hi, q);
+  byte_offs<3>(lo, o);
+  byte_offs<3>(hi, q);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     r.v[i] = tab8_issue(t, i, o[i]);
@@ -886,7 +761,7 @@ __global__ __launch_bounds__(kBlock * NV, (fused64_waves<P, U>())) void ec_encod
         int j = 0;
         for (; j + U <= k; j += U) {
           uint4 x[U];
-          load_grp<U>(x, sp, j, off, len);
+          enc_load_group<U, kNT>(x, sp, j, off, len);
           if constexpr (SL == 3)
             mac_feed_pipe<P, U, X0, PH>(acc, x, j, tbl + z, la + threadIdx.x, kLa, lt, x0src);
           else
@@ -894,7 +769,7 @@ __global__ __launch_bounds__(kBlock * NV, (fused64_waves<P, U>())) void ec_encod
         }
         for (; j < k; ++j) {
           uint4 x[1];
-          load_grp<1>(x, sp, j, off, len);
+          enc_load_group<1, kNT>(x, sp, j, off, len);
           mac_feed<P, 1, X0>(acc, x, j, tbl + z, feed, x0src);
         }
 #pragma unroll
@@ -911,7 +786,7 @@ __global__ __launch_bounds__(kBlock * NV, (fused64_waves<P, U>())) void ec_encod
         auto none = [](int, const uint4&) {};
         for (int j = 0; j < k; ++j) {
           uint4 x[1];
-          load_grp<1>(x, sp, j, off, len);
+          enc_load_group<1, kNT>(x, sp, j, off, len);
           mac_feed<P, 1, X0>(acc, x, j, tbl, none, x0src);
         }
 #pragma unroll
@@ -931,14 +806,6 @@ __global__ __launch_bounds__(kBlock * NV, (fused64_waves<P, U>())) void ec_encod
 #pragma unroll
     for (int l = 0; l < P; ++l) pp[(k + l) * sstep] = to_reg(ao[l]);
   }
-}
-
-// Sources per load group of the fused kernel: the largest candidate dividing k.
-int group_u(int k) {
-  static const int cand[] = {12, 10, 8, 6, 5, 4};
-  for (int u : cand)
-    if (k >= u && k % u == 0) return u;
-  return 4;
 }
 
 // 256-lane groups per workgroup: 2 when that fits more lane groups on a CU
@@ -991,7 +858,7 @@ void fused64_pass(unsigned grid, hipStream_t s, const uint64_t* ptrs, int ptr_st
                   const uint32_t* tbl, int len, int k, unsigned nitems,
                   const isal_hip_crc64_geom& g, const isal_hip_xrows& xr, int refl,
                   const uint64_t* tabs, uint64_t* part) {
-  switch (group_u(k)) {
+  switch (fused_group(k)) {
 #define FUSED64_U(u) \
   case u: launch_fused64<P, u>(grid, s, ptrs, ptr_stride, tbl, len, k, nitems, g, xr, refl, tabs, part); break;
     FUSED64_U(12) FUSED64_U(10) FUSED64_U(8) FUSED64_U(6) FUSED64_U(5)
@@ -1019,12 +886,12 @@ extern "C" void FUSED64_PART_FN(ISAL_FUSED64_PART)(
 
 #ifndef ISAL_FUSED64_PART
 
-int launch_combine64(const uint64_t* part, const uint64_t* ptrs, int ptr_stride, int nsh, int len,
-                     const isal_hip_crc64_geom& g, int refl, const uint64_t* tabs,
-                     uint64_t init_term, uint64_t* out, unsigned nshard, hipStream_t s) {
-  // four shards per workgroup at a time; each workgroup copies the 52 KB
-  // table set once, so the grid is capped at what is resident (3 per CU)
-  const unsigned want = (nshard + 3) / 4, grid = want < 768 ? want : 768;
+hipError_t launch_combine64(const uint64_t* part, const uint64_t* ptrs, int ptr_stride, int nsh, int len,
+                            const isal_hip_crc64_geom& g, int refl, const uint64_t* tabs,
+                            uint64_t init_term, uint64_t* out, unsigned nshard, hipStream_t s) {
+  // each workgroup copies the 52 KB table set once, so the grid is capped at
+  // what is resident (3 per CU)
+  const unsigned grid = combine_grid(nshard, 768);
   if (refl)
     ISAL_LAUNCH(crc64_combine<true>, dim3(grid), dim3(kBlock), 0, s, part, ptrs, ptr_stride,
                        nsh, len, static_cast<unsigned>(g.nblk), static_cast<unsigned>(g.nfull),
@@ -1034,7 +901,7 @@ int launch_combine64(const uint64_t* part, const uint64_t* ptrs, int ptr_stride,
                        nsh, len, static_cast<unsigned>(g.nblk), static_cast<unsigned>(g.nfull),
                        tabs, init_term, out, nshard);
   isal_hip_count_launch();
-  return static_cast<int>(hipGetLastError());
+  return hipGetLastError();
 }
 
 }  // namespace
@@ -1059,11 +926,9 @@ extern "C" int isal_hip_launch_crc64(const uint64_t* d_ptrs, int ptr_stride, int
   isal_hip_crc64_geom g;
   isal_hip_crc64_geometry(len, tt, &g);
   const unsigned long long per_stripe = static_cast<unsigned long long>(nsh) * (g.nblk ? g.nblk : 1);
-  const long long per = kMaxItems / per_stripe > 0 ? static_cast<long long>(kMaxItems / per_stripe) : 1;
-  for (long long s0 = 0; s0 < nstripes; s0 += per) {
-    const long long ns = nstripes - s0 < per ? nstripes - s0 : per;
-    const uint64_t* ptrs = d_ptrs + s0 * ptr_stride;
-    const unsigned nshard = static_cast<unsigned>(ns * nsh);
+  return for_slices(d_ptrs, ptr_stride, nstripes, crc_stripes_per_launch(per_stripe),
+                    [&](long long s0, unsigned ns, const uint64_t* ptrs) {
+    const unsigned nshard = ns * nsh;
     uint64_t* part = d_part + static_cast<size_t>(s0) * nsh * g.nblk * kBlock;
     if (g.nblk) {
       const unsigned nitems = static_cast<unsigned>(ns * nsh * g.nblk);
@@ -1077,13 +942,10 @@ extern "C" int isal_hip_launch_crc64(const uint64_t* d_ptrs, int ptr_stride, int
                            static_cast<unsigned>(g.nfull), d_tabs, part);
       isal_hip_count_launch();
       const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return static_cast<int>(e);
+      if (e != hipSuccess) return e;
     }
-    const int e = launch_combine64(part, ptrs, ptr_stride, nsh, len, g, refl, d_tabs, init_term,
-                                   out + s0 * nsh, nshard, s);
-    if (e) return e;
-  }
-  return 0;
+    return launch_combine64(part, ptrs, ptr_stride, nsh, len, g, refl, d_tabs, init_term, out + s0 * nsh, nshard, s);
+  });
 }
 
 extern "C" int isal_hip_launch_encode_crc64(const uint64_t* d_ptrs, int k, int rows,
@@ -1101,12 +963,9 @@ extern "C" int isal_hip_launch_encode_crc64(const uint64_t* d_ptrs, int k, int r
     return static_cast<int>(hipErrorInvalidValue);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int nsh = k + rows;
-  const long long per = static_cast<long long>(kMaxItems / g.nblk) > 0
-                            ? static_cast<long long>(kMaxItems / g.nblk) : 1;
-  for (long long s0 = 0; s0 < nstripes; s0 += per) {
-    const long long ns = nstripes - s0 < per ? nstripes - s0 : per;
+  return for_slices(d_ptrs, nsh, nstripes, crc_stripes_per_launch(g.nblk),
+                    [&](long long s0, unsigned ns, const uint64_t* ptrs) {
     const unsigned nitems = static_cast<unsigned>(ns * g.nblk);
-    const uint64_t* ptrs = d_ptrs + s0 * nsh;
     uint64_t* part = d_part + static_cast<size_t>(s0) * nsh * g.nblk * kBlock;
     switch (rows) {
 #define FUSED64_P(p) \
@@ -1116,13 +975,10 @@ extern "C" int isal_hip_launch_encode_crc64(const uint64_t* d_ptrs, int k, int r
 #undef FUSED64_P
     }
     isal_hip_count_launch();
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return static_cast<int>(e);
-    const int r = launch_combine64(part, ptrs, nsh, nsh, len, g, refl, d_tabs, init_term,
-                                   out + s0 * nsh, static_cast<unsigned>(ns * nsh), s);
-    if (r) return r;
-  }
-  return 0;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_combine64(part, ptrs, nsh, nsh, len, g, refl, d_tabs, init_term, out + s0 * nsh, ns * nsh, s);
+  });
 }
 
 extern "C" int isal_hip_launch_crc64_ragged(const uint64_t* d_ptrs, int nsh, const int* d_lens,
@@ -1146,10 +1002,9 @@ extern "C" int isal_hip_launch_crc64_combine_ragged(const uint64_t* d_part, cons
   if (nstripes <= 0 || nsh <= 0) return 0;
   const unsigned long long nshards = static_cast<unsigned long long>(nstripes) * static_cast<unsigned>(nsh);
   if (nshards > 0xFFFFFFFFull || tt < 1) return static_cast<int>(hipErrorInvalidValue);
-  // four shards per workgroup at a time; each workgroup copies its 41 KB of
-  // tables once, so the grid is capped at what is resident (3 per CU)
-  const unsigned long long want = (nshards + 3) / 4;
-  const unsigned grid = want < 768 ? static_cast<unsigned>(want) : 768u;
+  // each workgroup copies its 41 KB of tables once, so the grid is capped at
+  // what is resident (3 per CU)
+  const unsigned grid = combine_grid(nshards, 768);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (refl)
     ISAL_LAUNCH(crc64_combine_rag<true>, dim3(grid), dim3(kBlock), 0, s, d_part, d_ptrs, d_image, d_lens, d_first,

@@ -25,14 +25,12 @@
 
 #include <type_traits>
 
-#include "ec_device.h"
+#include "crc_device.h"
 
 namespace {
 
 constexpr uint32_t kCrcPoly = 0x82F63B78u;
 constexpr int kCrcTabDw = ISAL_HIP_CRC_TAB_DWORDS;
-
-static_assert(ISAL_HIP_CRC_TILE == kTile, "CRC tile = encode tile");
 
 __device__ __forceinline__ void load_crc_tables(uint32_t* lt, const uint32_t* __restrict__ tabs) {
   const uint4* src = reinterpret_cast<const uint4*>(tabs);
@@ -41,50 +39,7 @@ __device__ __forceinline__ void load_crc_tables(uint32_t* lt, const uint32_t* __
   __syncthreads();
 }
 
-// Byte offsets (entry index * 4) of the 7 fields of w, bits [0,5) [5,10)
-// [10,15) [15,20) [20,25) [25,30) [30,32): 11 VALU ops for 7 lookups. Shifting
-// w left by 2 puts every field at its entry's byte offset; masking the even
-// and the odd fields into separate words leaves two zero bits below each
-// field, so one bit-field extract yields the offset.
-// One v_bfe_u32. (Through the builtin, LLVM sees that the two low bits are
-// zero, narrows the mask to a non-contiguous one and emits shift + and.)
-template <int OFF, int WIDTH>
-__device__ __forceinline__ uint32_t bfe(uint32_t x) {
-  uint32_t r;
-  asm("v_bfe_u32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "n"(OFF), "n"(WIDTH));
-  return r;
-}
-
-__device__ __forceinline__ void field_offsets(uint32_t w, uint32_t (&o)[ISAL_HIP_CRC_FIELDS]) {
-  const uint32_t s = w << 2;
-  const uint32_t ev = s & 0x07C1F07Cu;  // fields 0, 2, 4 at [2,7) [12,17) [22,27)
-  const uint32_t od = s & 0xF83E0F80u;  // fields 1, 3, 5 at [7,12) [17,22) [27,32)
-  o[0] = ev & 0x7Cu;
-  o[1] = bfe<5, 7>(od);
-  o[2] = bfe<10, 7>(ev);
-  o[3] = bfe<15, 7>(od);
-  o[4] = bfe<20, 7>(ev);
-  o[5] = bfe<25, 7>(od);
-  o[6] = (w >> 28) & 0xCu;
-}
-
-// XOR of the 7 field lookups of w in the 7 consecutive 32-entry tables at t.
-__device__ __forceinline__ uint32_t lookup7(const uint32_t* t, uint32_t w) {
-  uint32_t o[ISAL_HIP_CRC_FIELDS];
-  field_offsets(w, o);
-  const char* b = reinterpret_cast<const char*>(t);
-  auto at = [&](int f) { return *reinterpret_cast<const uint32_t*>(b + f * 128 + o[f]); };
-  return xor3(xor3(at(0), at(1), at(2)), xor3(at(3), at(4), at(5)), at(6));
-}
-
-// The chunk map whose 28 field tables start at t, applied to a 16-byte chunk.
-__device__ __forceinline__ uint32_t chunk_map(const uint32_t* t, uint32_t w0, uint32_t w1,
-                                              uint32_t w2, uint32_t w3) {
-  constexpr int D = ISAL_HIP_CRC_FIELDS * 32;  // tables per dword of the chunk
-  return xor3(lookup7(t, w0), lookup7(t + D, w1), lookup7(t + 2 * D, w2)) ^ lookup7(t + 3 * D, w3);
-}
-
-// crc(0, 16 bytes): 28 conflict-free lookups.
+// crc(0, 16 bytes): 28 conflict-free lookups (chunk_map, crc_device.h).
 __device__ __forceinline__ __attribute__((unused)) uint32_t chunk_crc(const uint32_t* lt, uint32_t w0, uint32_t w1,
                                               uint32_t w2, uint32_t w3) {
   return chunk_map(lt + ISAL_HIP_CRC_CHUNK_TAB, w0, w1, w2, w3);
@@ -109,28 +64,16 @@ __device__ __forceinline__ uint32_t shift_tile(const uint32_t* lt, uint32_t a) {
 // map of the 16 chunk bytes, through byte-position tables:
 //   b' = P'(w0 ^ b, w1, w2, w3)   P' = Z^4080 o P   (P: crc(0, chunk) per byte)
 // and the block's last tile applies P instead, leaving the plain chain a.
-// 16 byte lookups per chunk, each offset one SDWA shift (byte select + << 2),
+// 16 byte lookups per chunk, each offset one SDWA shift (byte_offs: byte select + << 2),
 // no chain step; the 256-entry tables are not bank-conflict-free (8 entries
 // per bank): VALU issue traded for LDS cycles. LDS: P at 0, P' at 4096 dwords.
 [[maybe_unused]] constexpr int kPos = 0, kPosZ = 16 * 256, kPosLds = 32 * 256;
-
-__device__ __forceinline__ void byte_offs4(uint32_t w, uint32_t (&o)[4]) {
-  const uint32_t two = 2;
-  asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0"
-      : "=v"(o[0]) : "v"(two), "v"(w));
-  asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1"
-      : "=v"(o[1]) : "v"(two), "v"(w));
-  asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2"
-      : "=v"(o[2]) : "v"(two), "v"(w));
-  asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3"
-      : "=v"(o[3]) : "v"(two), "v"(w));
-}
 
 // r ^= the 4 byte lookups of dword d of a chunk in the position tables at t.
 __device__ __forceinline__ __attribute__((unused)) uint32_t lookup4b(uint32_t r, const uint32_t* t,
                                                                     int d, uint32_t w) {
   uint32_t o[4];
-  byte_offs4(w, o);
+  byte_offs<2>(w, o);
   const char* b = reinterpret_cast<const char*>(t + d * 1024);
   auto at = [&](int j) { return *reinterpret_cast<const uint32_t*>(b + j * 1024 + o[j]); };
   return xor3(xor3(r, at(0), at(1)), at(2), at(3));
@@ -198,20 +141,16 @@ __global__ __launch_bounds__(kBlock) void crc32c_shards_bytes(
     const unsigned stripe = si / nsh, i = si - stripe * nsh;
     const uint64_t base = ptrs[static_cast<size_t>(stripe) * ptr_stride + idx0 + i];
     const size_t shard = static_cast<size_t>(stripe) * nshard_total + shard0 + i;
-    const unsigned t0 = blk * tt, t1 = t0 + tt < ntiles ? t0 + tt : ntiles;
+    unsigned t0, t1;
+    block_tiles(blk, tt, ntiles, t0, t1);
     uint32_t a = 0;
     for (unsigned t = t0; t < t1; ++t) {
       const long long off = static_cast<long long>(t) * kTile + threadIdx.x * kVec;
-      const long long left = len - off;
-      const int nb = left >= kVec ? kVec : (left > 0 ? static_cast<int>(left) : 0);
+      const int nb = lane_bytes(len, off);
       uint32_t c = 0;
       if (nb == kVec) {
         const uint8_t* p = reinterpret_cast<const uint8_t*>(base) + off;
-        uint32_t v[4];
-#pragma unroll
-        for (int d = 0; d < 4; ++d)
-          v[d] = p[4 * d] | (p[4 * d + 1] << 8) | (p[4 * d + 2] << 16) | (static_cast<uint32_t>(p[4 * d + 3]) << 24);
-        c = chunk_crc(lt, v[0], v[1], v[2], v[3]);
+        c = chunk_crc(lt, le32(p), le32(p + 4), le32(p + 8), le32(p + 12));
       } else if (nb > 0) {
         c = bytes_crc(lt, reinterpret_cast<const uint8_t*>(base) + off, nb);
       }
@@ -229,67 +168,107 @@ __global__ __launch_bounds__(kBlock) void crc32c_shards_bytes(
 // register and maps the chunk once, b' = F'(w0 ^ b, w1, w2, w3) — 28 lookups
 // per tile and no Z^4096 step (35 before) — the block's last full tile applies
 // F (crc(0, chunk)) and leaves the plain chain. Double-buffered loads as above.
-// LDS: T0 (tail bytes), F (the CHUNK tables), F' (ISAL_HIP_CRC_FPRE_TAB).
+// LDS: T0 (tail bytes), F (the CHUNK tables), F' (at fpre of the image:
+// ISAL_HIP_CRC_FPRE_TAB of the uniform batch's, ISAL_HIP_CRC_RAG_FPRE of the
+// ragged batch's).
 constexpr int kPreF = ISAL_HIP_CRC_CHUNK_TAB, kPreFZ = kPreF + ISAL_HIP_CRC_CHUNK_DWORDS;
+constexpr int kPreLds = kPreFZ + ISAL_HIP_CRC_CHUNK_DWORDS;
+
+__device__ __forceinline__ void load_pre_tables(uint32_t* lt, const uint32_t* __restrict__ tabs, int fpre) {
+  for (int i = threadIdx.x; i < kPreFZ; i += kBlock) lt[i] = tabs[i];
+  for (int i = threadIdx.x; i < ISAL_HIP_CRC_CHUNK_DWORDS; i += kBlock) lt[kPreFZ + i] = tabs[fpre + i];
+  __syncthreads();
+}
+
+// One work item of the checksum-only pass, shared by crc32c_shards_pre and
+// crc32c_shards_rag: tiles [t0, t1) of the len-byte shard at base, of which
+// those below nfull are full. The lane's chain over the full tiles goes to
+// *part; the CRC of its chunk of the ragged tile, if the item has it, to *tail
+// (whole chunks by the field tables; the one lane that straddles len goes byte
+// by byte through T0 at lt).
+// step(last, b, x) maps chunk x with the chain b in its first dword through F
+// (last: the block's last full tile, or, with b = 0, a chunk of the ragged
+// tile) or F'. The kernels define it, where the tables are the LDS array
+// itself: with the choice between the two taken in here, on a pointer, the
+// uniform batch's pass ran 0.7 % slower (profiles/refactor_crc_ab.jsonl, run 1).
+template <class Step>
+__device__ __forceinline__ void crc32c_pass_item(const Step& step, const uint32_t* lt, uint64_t base, int len,
+                                                 unsigned t0, unsigned t1, unsigned nfull, uint32_t* part,
+                                                 uint32_t* tail) {
+  const long long lane = threadIdx.x * kVec;
+  const unsigned tf = t1 < nfull ? t1 : nfull;  // full tiles of this block
+  uint32_t b = 0;
+  unsigned t = t0;
+  uint4 xn[kCrcBatch];
+  if (t + kCrcBatch <= tf) {
+#pragma unroll
+    for (unsigned g = 0; g < kCrcBatch; ++g)
+      xn[g] = load16<kBufNT>(base, static_cast<long long>(t + g) * kTile + lane, len);
+  }
+  for (; t + kCrcBatch <= tf; t += kCrcBatch) {
+    uint4 x[kCrcBatch];
+#pragma unroll
+    for (unsigned g = 0; g < kCrcBatch; ++g) x[g] = xn[g];
+    if (t + 2 * kCrcBatch <= tf) {
+#pragma unroll
+      for (unsigned g = 0; g < kCrcBatch; ++g)
+        xn[g] = load16<kBufNT>(base, static_cast<long long>(t + kCrcBatch + g) * kTile + lane, len);
+    }
+#pragma unroll
+    for (unsigned g = 0; g < kCrcBatch; ++g) b = step(t + g + 1 == tf, b, x[g]);
+  }
+  for (; t < tf; ++t) b = step(t + 1 == tf, b, load16<kBufNT>(base, static_cast<long long>(t) * kTile + lane, len));
+  if (tf < t1) {  // the ragged tile
+    const long long off = static_cast<long long>(tf) * kTile + lane;
+    const int nb = lane_bytes(len, off);
+    uint32_t c = 0;
+    if (nb == kVec) {
+      c = step(true, 0u, load16<kBufNT>(base, off, len));
+    } else if (nb > 0) {
+      c = bytes_crc(lt, reinterpret_cast<const uint8_t*>(base) + off, nb);
+    }
+    *tail = c;
+  }
+  *part = b;
+}
 
 __global__ __launch_bounds__(kBlock) void crc32c_shards_pre(
     const uint64_t* __restrict__ ptrs, int ptr_stride, int idx0, int nsh, int len,
     unsigned nitems, unsigned nblk, unsigned tt, unsigned nfull, unsigned ntiles,
     const uint32_t* __restrict__ tabs, uint32_t* __restrict__ part, uint32_t* __restrict__ tail,
     int nshard_total, int shard0) {
-  __shared__ uint32_t lt[kPreFZ + ISAL_HIP_CRC_CHUNK_DWORDS];
-  for (int i = threadIdx.x; i < kPreFZ; i += kBlock) lt[i] = tabs[i];
-  for (int i = threadIdx.x; i < ISAL_HIP_CRC_CHUNK_DWORDS; i += kBlock)
-    lt[kPreFZ + i] = tabs[ISAL_HIP_CRC_FPRE_TAB + i];
-  __syncthreads();
-  const long long lane = threadIdx.x * kVec;
-  auto step = [&](unsigned t, unsigned tf, uint32_t b, const uint4& x) __attribute__((always_inline)) {
-    return t + 1 == tf ? chunk_map(lt + kPreF, x.x ^ b, x.y, x.z, x.w)
-                       : chunk_map(lt + kPreFZ, x.x ^ b, x.y, x.z, x.w);
+  __shared__ uint32_t lt[kPreLds];
+  load_pre_tables(lt, tabs, ISAL_HIP_CRC_FPRE_TAB);
+  auto step = [&](bool last, uint32_t b, const uint4& x) __attribute__((always_inline)) {
+    return last ? chunk_map(lt + kPreF, x.x ^ b, x.y, x.z, x.w) : chunk_map(lt + kPreFZ, x.x ^ b, x.y, x.z, x.w);
   };
   for (unsigned w = blockIdx.x; w < nitems; w += gridDim.x) {
     const unsigned si = w / nblk, blk = w - si * nblk;
     const unsigned stripe = si / nsh, i = si - stripe * nsh;
     const uint64_t base = ptrs[static_cast<size_t>(stripe) * ptr_stride + idx0 + i];
     const size_t shard = static_cast<size_t>(stripe) * nshard_total + shard0 + i;
-    const unsigned t0 = blk * tt, t1 = t0 + tt < ntiles ? t0 + tt : ntiles;
-    const unsigned tf = t1 < nfull ? t1 : nfull;  // full tiles of this block
-    uint32_t b = 0;
-    unsigned t = t0;
-    uint4 xn[kCrcBatch];
-    if (t + kCrcBatch <= tf) {
-#pragma unroll
-      for (unsigned g = 0; g < kCrcBatch; ++g)
-        xn[g] = load16<kBufNT>(base, static_cast<long long>(t + g) * kTile + lane, len);
-    }
-    for (; t + kCrcBatch <= tf; t += kCrcBatch) {
-      uint4 x[kCrcBatch];
-#pragma unroll
-      for (unsigned g = 0; g < kCrcBatch; ++g) x[g] = xn[g];
-      if (t + 2 * kCrcBatch <= tf) {
-#pragma unroll
-        for (unsigned g = 0; g < kCrcBatch; ++g)
-          xn[g] = load16<kBufNT>(base, static_cast<long long>(t + kCrcBatch + g) * kTile + lane, len);
-      }
-#pragma unroll
-      for (unsigned g = 0; g < kCrcBatch; ++g) b = step(t + g, tf, b, x[g]);
-    }
-    for (; t < tf; ++t) b = step(t, tf, b, load16<kBufNT>(base, static_cast<long long>(t) * kTile + lane, len));
-    if (tf < t1) {  // the ragged tile: its chunk CRCs go to tail[]
-      const long long off = static_cast<long long>(tf) * kTile + lane;
-      const long long left = len - off;
-      const int nb = left >= kVec ? kVec : (left > 0 ? static_cast<int>(left) : 0);
-      uint32_t c = 0;
-      if (nb == kVec) {
-        const uint4 x = load16<kBufNT>(base, off, len);
-        c = chunk_map(lt + kPreF, x.x, x.y, x.z, x.w);
-      } else if (nb > 0) {
-        c = bytes_crc(lt, reinterpret_cast<const uint8_t*>(base) + off, nb);
-      }
-      tail[shard * kBlock + threadIdx.x] = c;
-    }
-    part[(shard * nblk + blk) * kBlock + threadIdx.x] = b;
+    unsigned t0, t1;
+    block_tiles(blk, tt, ntiles, t0, t1);
+    crc32c_pass_item(step, lt, base, len, t0, t1, nfull, part + (shard * nblk + blk) * kBlock + threadIdx.x,
+                     tail + shard * kBlock + threadIdx.x);
   }
+}
+
+// One Horner step of a lane's four lane positions across a shard's blocks:
+// h[j] = K(h[j]) ^ p[j], K a multiplication as four byte tables at k4.
+__device__ __forceinline__ void horner4(uint32_t (&h)[4], const uint32_t* k4, const uint4& p) {
+  const uint32_t pv[4] = {p.x, p.y, p.z, p.w};
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    h[j] = xor3(k4[h[j] & 0xff], k4[256 + ((h[j] >> 8) & 0xff)], k4[512 + ((h[j] >> 16) & 0xff)]) ^
+           k4[768 + (h[j] >> 24)] ^ pv[j];
+}
+
+// XOR over the wave (every lane ends up with it).
+__device__ __forceinline__ uint32_t wave_xor(uint32_t v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v ^= __shfl_xor(v, m, 64);
+  return v;
 }
 
 // ---------------------------------------------------------------------------
@@ -319,15 +298,9 @@ __global__ __launch_bounds__(kBlock) void crc32c_combine(
   for (unsigned sh = blockIdx.x * kWaves + (threadIdx.x >> 6); sh < nsh; sh += gridDim.x * kWaves) {
     const uint32_t* pp = part + static_cast<size_t>(sh) * nblk * kBlock + 4 * lane;
     uint32_t h[4] = {0, 0, 0, 0};
-    for (unsigned b = 0; b < nblk; ++b) {
-      const uint32_t* k4 = (b + 1 == nblk) ? kt + ISAL_HIP_CRC_PLAN_LAST : kt + ISAL_HIP_CRC_PLAN_BLOCK;
-      const uint4 p = *reinterpret_cast<const uint4*>(pp + static_cast<size_t>(b) * kBlock);
-      const uint32_t pv[4] = {p.x, p.y, p.z, p.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        h[j] = xor3(k4[h[j] & 0xff], k4[256 + ((h[j] >> 8) & 0xff)], k4[512 + ((h[j] >> 16) & 0xff)]) ^
-               k4[768 + (h[j] >> 24)] ^ pv[j];
-    }
+    for (unsigned b = 0; b < nblk; ++b)
+      horner4(h, (b + 1 == nblk) ? kt + ISAL_HIP_CRC_PLAN_LAST : kt + ISAL_HIP_CRC_PLAN_BLOCK,
+              *reinterpret_cast<const uint4*>(pp + static_cast<size_t>(b) * kBlock));
     uint32_t v = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) v ^= crc_mulmod(h[j], w4[j]);
@@ -335,34 +308,27 @@ __global__ __launch_bounds__(kBlock) void crc32c_combine(
       const uint4 t = reinterpret_cast<const uint4*>(tail + static_cast<size_t>(sh) * kBlock)[lane];
       v ^= crc_mulmod(t.x, c4[0]) ^ crc_mulmod(t.y, c4[1]) ^ crc_mulmod(t.z, c4[2]) ^ crc_mulmod(t.w, c4[3]);
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v ^= __shfl_xor(v, m, 64);
+    v = wave_xor(v);
     if (lane == 0) out[sh] = v ^ iterm;
   }
 }
 
 // ---------------------------------------------------------------------------
 // Ragged: stripe s has its own shard length lens[s] (isal_hip_internal.h
-// "ragged CRC32C"). The pass is crc32c_shards_pre's body with the length, the
-// tile range and the full-tile count read per item: workgroup w takes row
-// w / nsh of the {stripe, block} item table and shard w % nsh of that stripe.
-// Shards are 16-byte aligned by contract; the buffer descriptor of a shard is
-// bounded by its own length, and only whole chunks below it are loaded (the
-// one lane that straddles the length goes byte by byte).
+// "ragged CRC32C"). The pass is crc32c_pass_item with the length, the tile
+// range and the full-tile count read per item: workgroup w takes row w / nsh
+// of the {stripe, block} item table and shard w % nsh of that stripe. Shards
+// are 16-byte aligned by contract; the buffer descriptor of a shard is
+// bounded by its own length, and only whole chunks below it are loaded.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void crc32c_shards_rag(
     const uint64_t* __restrict__ ptrs, int nsh, const int* __restrict__ lens,
     const unsigned* __restrict__ items, unsigned nwork, unsigned tt,
     const uint32_t* __restrict__ tabs, uint32_t* __restrict__ part, uint32_t* __restrict__ tail) {
-  __shared__ uint32_t lt[kPreFZ + ISAL_HIP_CRC_CHUNK_DWORDS];
-  for (int i = threadIdx.x; i < kPreFZ; i += kBlock) lt[i] = tabs[i];
-  for (int i = threadIdx.x; i < ISAL_HIP_CRC_CHUNK_DWORDS; i += kBlock)
-    lt[kPreFZ + i] = tabs[ISAL_HIP_CRC_RAG_FPRE + i];
-  __syncthreads();
-  const long long lane = threadIdx.x * kVec;
-  auto step = [&](unsigned t, unsigned tf, uint32_t b, const uint4& x) __attribute__((always_inline)) {
-    return t + 1 == tf ? chunk_map(lt + kPreF, x.x ^ b, x.y, x.z, x.w)
-                       : chunk_map(lt + kPreFZ, x.x ^ b, x.y, x.z, x.w);
+  __shared__ uint32_t lt[kPreLds];
+  load_pre_tables(lt, tabs, ISAL_HIP_CRC_RAG_FPRE);
+  auto step = [&](bool last, uint32_t b, const uint4& x) __attribute__((always_inline)) {
+    return last ? chunk_map(lt + kPreF, x.x ^ b, x.y, x.z, x.w) : chunk_map(lt + kPreFZ, x.x ^ b, x.y, x.z, x.w);
   };
   for (unsigned w = blockIdx.x; w < nwork; w += gridDim.x) {
     const unsigned item = w / nsh, i = w - item * nsh;
@@ -371,43 +337,10 @@ __global__ __launch_bounds__(kBlock) void crc32c_shards_rag(
     const uint64_t base = ptrs[static_cast<size_t>(stripe) * nsh + i];
     const unsigned nfull = static_cast<unsigned>(len) / kTile;
     const unsigned ntiles = nfull + (static_cast<unsigned>(len) % kTile ? 1u : 0u);
-    const unsigned t0 = blk * tt, t1 = t0 + tt < ntiles ? t0 + tt : ntiles;
-    const unsigned tf = t1 < nfull ? t1 : nfull;  // full tiles of this block
-    uint32_t b = 0;
-    unsigned t = t0;
-    uint4 xn[kCrcBatch];
-    if (t + kCrcBatch <= tf) {
-#pragma unroll
-      for (unsigned g = 0; g < kCrcBatch; ++g)
-        xn[g] = load16<kBufNT>(base, static_cast<long long>(t + g) * kTile + lane, len);
-    }
-    for (; t + kCrcBatch <= tf; t += kCrcBatch) {
-      uint4 x[kCrcBatch];
-#pragma unroll
-      for (unsigned g = 0; g < kCrcBatch; ++g) x[g] = xn[g];
-      if (t + 2 * kCrcBatch <= tf) {
-#pragma unroll
-        for (unsigned g = 0; g < kCrcBatch; ++g)
-          xn[g] = load16<kBufNT>(base, static_cast<long long>(t + kCrcBatch + g) * kTile + lane, len);
-      }
-#pragma unroll
-      for (unsigned g = 0; g < kCrcBatch; ++g) b = step(t + g, tf, b, x[g]);
-    }
-    for (; t < tf; ++t) b = step(t, tf, b, load16<kBufNT>(base, static_cast<long long>(t) * kTile + lane, len));
-    if (tf < t1) {  // the ragged tile: its chunk CRCs go to the shard's tail slot
-      const long long off = static_cast<long long>(tf) * kTile + lane;
-      const long long left = len - off;
-      const int nb = left >= kVec ? kVec : (left > 0 ? static_cast<int>(left) : 0);
-      uint32_t c = 0;
-      if (nb == kVec) {
-        const uint4 x = load16<kBufNT>(base, off, len);
-        c = chunk_map(lt + kPreF, x.x, x.y, x.z, x.w);
-      } else if (nb > 0) {
-        c = bytes_crc(lt, reinterpret_cast<const uint8_t*>(base) + off, nb);
-      }
-      tail[(static_cast<size_t>(stripe) * nsh + i) * kBlock + threadIdx.x] = c;
-    }
-    part[static_cast<size_t>(w) * kBlock + threadIdx.x] = b;
+    unsigned t0, t1;
+    block_tiles(blk, tt, ntiles, t0, t1);
+    crc32c_pass_item(step, lt, base, len, t0, t1, nfull, part + static_cast<size_t>(w) * kBlock + threadIdx.x,
+                     tail + (static_cast<size_t>(stripe) * nsh + i) * kBlock + threadIdx.x);
   }
 }
 
@@ -454,14 +387,7 @@ __global__ __launch_bounds__(kBlock) void crc32c_combine_rag(
     const uint32_t* pp = part + (static_cast<size_t>(first[stripe]) * nsh + i) * kBlock + 4 * lane;
     const size_t bstride = static_cast<size_t>(nsh) * kBlock;
     uint32_t h[4] = {0, 0, 0, 0};
-    for (unsigned b = 0; b + 1 < nblk; ++b) {
-      const uint4 p = *reinterpret_cast<const uint4*>(pp + b * bstride);
-      const uint32_t pv[4] = {p.x, p.y, p.z, p.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        h[j] = xor3(kt[h[j] & 0xff], kt[256 + ((h[j] >> 8) & 0xff)], kt[512 + ((h[j] >> 16) & 0xff)]) ^
-               kt[768 + (h[j] >> 24)] ^ pv[j];
-    }
+    for (unsigned b = 0; b + 1 < nblk; ++b) horner4(h, kt, *reinterpret_cast<const uint4*>(pp + b * bstride));
     {  // the last block: nfull_last <= tt full tiles
       const uint4 p = *reinterpret_cast<const uint4*>(pp + (nblk - 1) * bstride);
       const uint32_t pv[4] = {p.x, p.y, p.z, p.w};
@@ -486,14 +412,11 @@ __global__ __launch_bounds__(kBlock) void crc32c_combine_rag(
         v ^= crc_mulmod(tv[j], X[rest > 0 ? rest : 0]);
       }
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v ^= __shfl_xor(v, m, 64);
+    v = wave_xor(v);
     const uint32_t xfull = wave_product32(((nfull >> (lane & 31)) & 1u) ? sq : 0x80000000u);
     if (lane == 0) out[sh] = v ^ crc_mulmod(init, crc_mulmod(xfull, X[r]));
   }
 }
-
-constexpr unsigned kMaxCrcItems = 1u << 30;
 
 unsigned crc_grid(unsigned long long nitems) {
   return static_cast<unsigned>(nitems);
@@ -552,46 +475,13 @@ struct SrcFeed {
   }
 };
 
-// acc ^= the U sources x[] (sources j..j+U-1) times their coefficients; each
-// source also feeds its CRC chain.
-template <int P, int U, bool R0 = false, class Feed>
-__device__ __forceinline__ void mac_feed16(uint32_t (&acc)[P][4], const uint4 (&x)[U], int j,
-                                           const uint32_t* __restrict__ tbl, const Feed& feed, unsigned long long x0src = 0) {
-  constexpr int PAIR = P <= 4 ? 2 : 1;
-#pragma unroll
-  for (int u = 0; u + PAIR <= U; u += PAIR) {
-    if constexpr (PAIR == 2) {
-      mac16x2<P, R0>(acc, x[u], x[u + 1], tbl + (j + u) * P * kTbl, tbl + (j + u + 1) * P * kTbl,
-                     r0_mask(x0src, j + u), r0_mask(x0src, j + u + 1));
-      feed(j + u, x[u]);
-      feed(j + u + 1, x[u + 1]);
-    } else {
-      mac16<P, R0>(acc, x[u], tbl + (j + u) * P * kTbl, r0_mask(x0src, j + u));
-      feed(j + u, x[u]);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  if constexpr (PAIR == 2 && (U & 1)) {
-    mac16<P, R0>(acc, x[U - 1], tbl + (j + U - 1) * P * kTbl, r0_mask(x0src, j + U - 1));
-    feed(j + U - 1, x[U - 1]);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-template <int U, int MODE>
-__device__ __forceinline__ void load_group(uint4 (&x)[U], const uint64_t* __restrict__ sp, int j,
-                                           long long off, int len) {
-#pragma unroll
-  for (int u = 0; u < U; ++u) x[u] = load16<MODE>(sp[j + u], off, len);
-}
-
 template <int P, int U, int MODE, bool R0, class Feed>
 __device__ __forceinline__ void chunk16_crc(uint32_t (&acc)[P][4], const uint64_t* __restrict__ sp,
                                             int j, long long off, const uint32_t* __restrict__ tbl,
                                             int len, const Feed& feed, unsigned long long x0src) {
   uint4 x[U];
-  load_group<U, MODE>(x, sp, j, off, len);
-  mac_feed16<P, U, R0>(acc, x, j, tbl, feed, x0src);
+  enc_load_group<U, MODE>(x, sp, j, off, len);
+  mac_feed<P, U, R0>(acc, x, j, tbl, feed, x0src);
 }
 
 // REG: k == U, one load group whose chains are indexed at compile time.
@@ -707,21 +597,21 @@ __global__ __launch_bounds__(kBlock * NV, (crc_waves<P, Pol::U, REG>())) void ec
       // tile's GF and CRC work runs (the CRC lookups otherwise leave HBM idle).
       uint4 xn[Pol::U];
       if (t0 < tf)
-        load_group<Pol::U, Pol::LD>(xn, sp + src0, 0, static_cast<long long>(t0) * kTile + tid * kVec,
+        enc_load_group<Pol::U, Pol::LD>(xn, sp + src0, 0, static_cast<long long>(t0) * kTile + tid * kVec,
                                     len);
       for (unsigned t = t0; t < tf; ++t) {
         const long long off = static_cast<long long>(t) * kTile + tid * kVec;
         uint4 x[Pol::U];
 #pragma unroll
         for (int u = 0; u < Pol::U; ++u) x[u] = xn[u];
-        if (t + 1 < tf) load_group<Pol::U, Pol::LD>(xn, sp + src0, 0, off + kTile, len);
+        if (t + 1 < tf) enc_load_group<Pol::U, Pol::LD>(xn, sp + src0, 0, off + kTile, len);
         uint32_t acc[P][4];
 #pragma unroll
         for (int l = 0; l < P; ++l) acc[l][0] = acc[l][1] = acc[l][2] = acc[l][3] = 0;
         int z = 0;  // opaque zero: see below
         asm volatile("" : "+s"(z));
         with_last(t + 1 == tf, [&](auto lastc) __attribute__((always_inline)) {
-          mac_feed16<P, Pol::U, X0>(acc, x, 0, tbl + z,
+          mac_feed<P, Pol::U, X0>(acc, x, 0, tbl + z,
                                     SrcFeed<kFull, NB, decltype(lastc)::value>{
                                         lt, la, ra, tail + shard_s * kBlock, kLa, tid},
                                     x0src);
@@ -805,13 +695,6 @@ __global__ __launch_bounds__(kBlock * NV, (crc_waves<P, Pol::U, REG>())) void ec
 template <int UU>
 using FusedPol = EncPol<UU, kNT, kNT>;
 
-int enc_group_crc(int k) {
-  static const int cand[] = {12, 10, 8, 6, 5, 4};
-  for (int u : cand)
-    if (k >= u && k % u == 0) return u;
-  return 4;
-}
-
 // 256-lane groups per workgroup of the fused kernel: 2 when that fits more
 // groups on a CU (160 KiB of LDS: 32 KiB of byte tables per workgroup, 1 KiB
 // of chains per source and group), else 1.
@@ -865,7 +748,7 @@ void fused_pass(unsigned grid, size_t lds, hipStream_t s, const uint64_t* ptrs, 
 #define FUSED_U(u)                                                                               \
   launch_fused<P, u>(grid, lds, s, ptrs, ptr_stride, src0, dst0, tbl, len, k, nitems, g, xr,   \
                      tabs, part, tail, nshard_total, crc_src, out_shard0)
-  switch (enc_group_crc(k)) {
+  switch (fused_group(k)) {
     case 12: FUSED_U(12); break;
     case 10: FUSED_U(10); break;
     case 8: FUSED_U(8); break;
@@ -915,12 +798,9 @@ extern "C" int isal_hip_launch_crc(const uint64_t* d_ptrs, int ptr_stride, int i
   isal_hip_crc_geom g;
   isal_hip_crc_geometry(len, tt, &g);
   const unsigned long long per_stripe = static_cast<unsigned long long>(nsh) * g.nblk;
-  const long long per = static_cast<long long>(kMaxCrcItems / per_stripe) > 0
-                            ? static_cast<long long>(kMaxCrcItems / per_stripe) : 1;
-  for (long long s0 = 0; s0 < nstripes; s0 += per) {
-    const long long ns = nstripes - s0 < per ? nstripes - s0 : per;
+  return for_slices(d_ptrs, ptr_stride, nstripes, crc_stripes_per_launch(per_stripe),
+                    [&](long long s0, unsigned ns, const uint64_t* ptrs) {
     const unsigned nitems = static_cast<unsigned>(ns * per_stripe);
-    const uint64_t* ptrs = d_ptrs + s0 * ptr_stride;
     uint32_t* part = d_part + static_cast<size_t>(s0) * nshard_total * g.nblk * kBlock;
     uint32_t* tail = d_tail + static_cast<size_t>(s0) * nshard_total * kBlock;
     if (vec16)
@@ -934,10 +814,8 @@ extern "C" int isal_hip_launch_crc(const uint64_t* d_ptrs, int ptr_stride, int i
                          static_cast<unsigned>(tt), static_cast<unsigned>(g.nfull),
                          static_cast<unsigned>(g.ntiles), d_tabs, part, tail, nshard_total, shard0);
     isal_hip_count_launch();
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return static_cast<int>(e);
-  }
-  return 0;
+    return hipGetLastError();
+  });
 }
 
 extern "C" int isal_hip_launch_encode_crc(const uint64_t* d_ptrs, int ptr_stride, int src_idx0,
@@ -951,12 +829,9 @@ extern "C" int isal_hip_launch_encode_crc(const uint64_t* d_ptrs, int ptr_stride
   isal_hip_crc_geom g;
   isal_hip_crc_geometry(len, tt, &g);
   const int nshard_total = k + rows;
-  const long long per = static_cast<long long>(kMaxCrcItems / g.nblk) > 0
-                            ? static_cast<long long>(kMaxCrcItems / g.nblk) : 1;
-  for (long long s0 = 0; s0 < nstripes; s0 += per) {
-    const long long ns = nstripes - s0 < per ? nstripes - s0 : per;
+  return for_slices(d_ptrs, ptr_stride, nstripes, crc_stripes_per_launch(g.nblk),
+                    [&](long long s0, unsigned ns, const uint64_t* ptrs) {
     const unsigned nitems = static_cast<unsigned>(ns * g.nblk);
-    const uint64_t* ptrs = d_ptrs + s0 * ptr_stride;
     uint32_t* part = d_part + static_cast<size_t>(s0) * nshard_total * g.nblk * kBlock;
     uint32_t* tail = d_tail + static_cast<size_t>(s0) * nshard_total * kBlock;
     for (int r0 = 0; r0 < rows; r0 += EC_MAX_ROWS_PER_PASS) {
@@ -979,10 +854,10 @@ extern "C" int isal_hip_launch_encode_crc(const uint64_t* d_ptrs, int ptr_stride
       }
       isal_hip_count_launch();
       const hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return static_cast<int>(e);
+      if (e != hipSuccess) return e;
     }
-  }
-  return 0;
+    return hipSuccess;
+  });
 }
 
 extern "C" int isal_hip_launch_crc_combine(const uint32_t* d_part, const uint32_t* d_tail,
@@ -991,9 +866,7 @@ extern "C" int isal_hip_launch_crc_combine(const uint32_t* d_part, const uint32_
                                            void* stream) {
   if (nsh <= 0) return 0;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const unsigned long long want = (static_cast<unsigned long long>(nsh) + 3) / 4;  // four shards per workgroup
-  const unsigned grid = want < 2048 ? static_cast<unsigned>(want) : 2048u;
-  ISAL_LAUNCH(crc32c_combine, dim3(grid), dim3(kBlock), 0, s, d_part, d_tail, d_plan,
+  ISAL_LAUNCH(crc32c_combine, dim3(combine_grid(nsh, 2048)), dim3(kBlock), 0, s, d_part, d_tail, d_plan,
                      static_cast<unsigned>(nblk), has_tail, init, out, static_cast<unsigned>(nsh));
   isal_hip_count_launch();
   return static_cast<int>(hipGetLastError());
@@ -1005,7 +878,7 @@ extern "C" int isal_hip_launch_crc_ragged(const uint64_t* d_ptrs, int nsh, const
                                           void* stream) {
   if (nitems == 0 || nsh <= 0) return 0;
   const unsigned long long nwork = static_cast<unsigned long long>(nitems) * static_cast<unsigned>(nsh);
-  if (nwork > kMaxCrcItems || tt < 1) return static_cast<int>(hipErrorInvalidValue);
+  if (nwork > kMaxItems || tt < 1) return static_cast<int>(hipErrorInvalidValue);
   ISAL_LAUNCH(crc32c_shards_rag, dim3(crc_grid(nwork)), dim3(kBlock), 0, static_cast<hipStream_t>(stream),
               d_ptrs, nsh, d_lens, d_items, static_cast<unsigned>(nwork), static_cast<unsigned>(tt), d_image,
               d_part, d_tail);
@@ -1021,11 +894,9 @@ extern "C" int isal_hip_launch_crc_combine_ragged(const uint32_t* d_part, const 
   if (nstripes <= 0 || nsh <= 0) return 0;
   const unsigned long long nshards = static_cast<unsigned long long>(nstripes) * static_cast<unsigned>(nsh);
   if (nshards > 0xFFFFFFFFull || tt < 1) return static_cast<int>(hipErrorInvalidValue);
-  const unsigned long long want = (nshards + 3) / 4;  // four shards per workgroup
-  const unsigned grid = want < 2048 ? static_cast<unsigned>(want) : 2048u;
-  ISAL_LAUNCH(crc32c_combine_rag, dim3(grid), dim3(kBlock), 0, static_cast<hipStream_t>(stream), d_part,
-              d_tail, d_image, d_lens, d_first, static_cast<unsigned>(nsh), static_cast<unsigned>(tt), init,
-              out, static_cast<unsigned>(nshards));
+  ISAL_LAUNCH(crc32c_combine_rag, dim3(combine_grid(nshards, 2048)), dim3(kBlock), 0,
+              static_cast<hipStream_t>(stream), d_part, d_tail, d_image, d_lens, d_first,
+              static_cast<unsigned>(nsh), static_cast<unsigned>(tt), init, out, static_cast<unsigned>(nshards));
   isal_hip_count_launch();
   return static_cast<int>(hipGetLastError());
 }

@@ -16,7 +16,8 @@
 //    bytes of chunk 0 as a CRC register is, so raw(0, .) of the chunks joined
 //    is raw(start, whole chunks) with no Z^n(init) term;
 //  * lane value h = raw(0, chunk) by the conflict-free 5-bit field tables
-//    (crc_host.c / crc64_host.c, the layout of the whole-shard kernels);
+//    (crc_host.c / crc64_host.c; the layout and the lookups, crc_device.h, of
+//    the whole-shard kernels);
 //  * log-step join, crc(A || B) = Z^|B|(crc A) ^ crc B: step d maps h through
 //    Z^(16 * 2^d) and XORs the value 2^d lanes up; after log2(min(m, 64))
 //    steps position 0 of each sector (or of each wave) holds its bytes' CRC;
@@ -31,90 +32,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "ec_device.h"
+#include "crc_device.h"
 
 namespace {
 
-constexpr int kF = ISAL_HIP_CRC_FIELDS;
-static_assert(ISAL_HIP_CRC_TILE == kTile, "CRC tile = encode tile");
-static_assert(kF == 7, "field layout below assumes 7 fields per dword");
 static_assert(kBlock == 256, "four waves of 64 lanes per tile");
 
-template <int OFF, int WIDTH>
-__device__ __forceinline__ uint32_t bfe(uint32_t x) {
-  uint32_t r;
-  asm("v_bfe_u32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "n"(OFF), "n"(WIDTH));
-  return r;
-}
-
-// ---- CRC32C: 32-entry dword tables (as crc_kernels.hip) -------------------
-// Byte offsets (entry index * 4) of the 7 fields of w, bits [0,5) [5,10) ...
-// [25,30) [30,32).
-__device__ __forceinline__ void field_offsets4(uint32_t w, uint32_t (&o)[kF]) {
-  const uint32_t s = w << 2;
-  const uint32_t ev = s & 0x07C1F07Cu;  // fields 0, 2, 4 at [2,7) [12,17) [22,27)
-  const uint32_t od = s & 0xF83E0F80u;  // fields 1, 3, 5 at [7,12) [17,22) [27,32)
-  o[0] = ev & 0x7Cu;
-  o[1] = bfe<5, 7>(od);
-  o[2] = bfe<10, 7>(ev);
-  o[3] = bfe<15, 7>(od);
-  o[4] = bfe<20, 7>(ev);
-  o[5] = bfe<25, 7>(od);
-  o[6] = (w >> 28) & 0xCu;
-}
-
-// XOR of the 7 field lookups of w in the 7 consecutive 32-entry tables at t.
-__device__ __forceinline__ uint32_t lookup7(const uint32_t* t, uint32_t w) {
-  uint32_t o[kF];
-  field_offsets4(w, o);
-  const char* b = reinterpret_cast<const char*>(t);
-  auto at = [&](int f) { return *reinterpret_cast<const uint32_t*>(b + f * 128 + o[f]); };
-  return xor3(xor3(at(0), at(1), at(2)), xor3(at(3), at(4), at(5)), at(6));
-}
-
-// ---- crc64: 32-entry qword tables (as crc64_kernels.hip) ------------------
-__device__ __forceinline__ void field_offsets8(uint32_t w, uint32_t (&o)[kF]) {
-  const uint32_t s = w << 3;
-  const uint32_t ev = s & 0x0F83E0F8u;  // fields 0, 2, 4 at [3,8) [13,18) [23,28)
-  const uint32_t od = s & 0x007C1F00u;  // fields 1, 3 at [8,13) [18,23)
-  o[0] = ev & 0xF8u;
-  o[1] = bfe<5, 8>(od);
-  o[2] = bfe<10, 8>(ev);
-  o[3] = bfe<15, 8>(od);
-  o[4] = bfe<20, 8>(ev);
-  o[5] = (w >> 22) & 0xF8u;
-  o[6] = (w >> 27) & 0x18u;
-}
-
-struct X64 {
-  uint32_t lo, hi;
-  __device__ __forceinline__ void add2(uint64_t x, uint64_t y) {
-    lo = xor3(lo, static_cast<uint32_t>(x), static_cast<uint32_t>(y));
-    hi = xor3(hi, static_cast<uint32_t>(x >> 32), static_cast<uint32_t>(y >> 32));
-  }
-  __device__ __forceinline__ uint64_t get() const { return (static_cast<uint64_t>(hi) << 32) | lo; }
-};
-
-__device__ __forceinline__ uint64_t tab_at(const uint64_t* t, int f, uint32_t o) {
-  return *reinterpret_cast<const uint64_t*>(reinterpret_cast<const char*>(t) + f * 256 + o);
-}
-
-// acc ^= the 14 field lookups of the dwords (w0, w1) in the 14 tables at t.
-__device__ __forceinline__ void lookup14(X64& acc, const uint64_t* t, uint32_t w0, uint32_t w1) {
-  uint32_t o[kF], q[kF];
-  field_offsets8(w0, o);
-  field_offsets8(w1, q);
-  const uint64_t* u = t + kF * 32;
-  acc.add2(tab_at(t, 0, o[0]), tab_at(t, 1, o[1]));
-  acc.add2(tab_at(t, 2, o[2]), tab_at(t, 3, o[3]));
-  acc.add2(tab_at(t, 4, o[4]), tab_at(t, 5, o[5]));
-  acc.add2(tab_at(t, 6, o[6]), tab_at(u, 0, q[0]));
-  acc.add2(tab_at(u, 1, q[1]), tab_at(u, 2, q[2]));
-  acc.add2(tab_at(u, 3, q[3]), tab_at(u, 4, q[4]));
-  acc.add2(tab_at(u, 5, q[5]), tab_at(u, 6, q[6]));
-}
-
 // ---- what the one kernel body needs of a checksum family -------------------
+// The table lookups are crc_device.h's, shared with the whole-shard kernels:
+// lookup7 / chunk_map on CRC32C's dword tables, apply_op / chunk_acc on crc64's
+// qword tables.
 // start: the register a sector starts from (init; ~init for crc64). poly and
 // refl: the byte step's polynomial (x^N implicit, in the register's bit order)
 // and direction.
@@ -123,7 +50,7 @@ struct Crc32c {
   static constexpr int kImage = ISAL_HIP_SECTOR32_DWORDS, kChunk = ISAL_HIP_CRC_CHUNK_DWORDS, kOp = kF * 32;
   static __device__ __forceinline__ void inject(uint4& x, reg start, int) { x.x ^= start; }
   static __device__ __forceinline__ reg chunk(const reg* lt, const uint4& x) {
-    return xor3(lookup7(lt, x.x), lookup7(lt + kOp, x.y), lookup7(lt + 2 * kOp, x.z)) ^ lookup7(lt + 3 * kOp, x.w);
+    return chunk_map(lt, x.x, x.y, x.z, x.w);
   }
   static __device__ __forceinline__ reg zmap(const reg* lt, int d, reg h) { return lookup7(lt + kChunk + d * kOp, h); }
   static __device__ __forceinline__ reg up(reg h, unsigned by) { return __shfl_down(h, by, 64); }
@@ -149,15 +76,10 @@ struct Crc64 {
   }
   static __device__ __forceinline__ reg chunk(const reg* lt, const uint4& x) {
     X64 a{0u, 0u};
-    lookup14(a, lt, x.x, x.y);
-    lookup14(a, lt + 2 * kF * 32, x.z, x.w);
+    chunk_acc(a, lt, x.x, x.y, x.z, x.w);
     return a.get();
   }
-  static __device__ __forceinline__ reg zmap(const reg* lt, int d, reg h) {
-    X64 a{0u, 0u};
-    lookup14(a, lt + kChunk + d * kOp, static_cast<uint32_t>(h), static_cast<uint32_t>(h >> 32));
-    return a.get();
-  }
+  static __device__ __forceinline__ reg zmap(const reg* lt, int d, reg h) { return apply_op(lt + kChunk + d * kOp, h); }
   static __device__ __forceinline__ reg up(reg h, unsigned by) {
     const uint32_t lo = __shfl_down(static_cast<uint32_t>(h), by, 64);
     const uint32_t hi = __shfl_down(static_cast<uint32_t>(h >> 32), by, 64);

@@ -1,7 +1,8 @@
 // ec_device.h — device-side building blocks shared by the GF(2^8) kernels
-// (ec_kernels.hip) and the fused encode+CRC kernels (crc_kernels.hip).
-// Included by exactly those translation units; everything lives in an
-// anonymous namespace (one private copy per kernel object).
+// (ec_kernels.hip) and, through crc_device.h, the checksum and fused
+// encode+CRC kernels (crc_kernels.hip, crc64_kernels.hip,
+// crc_sector_kernels.hip). Included by exactly those translation units;
+// everything lives in an anonymous namespace (one private copy per kernel object).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -37,6 +38,22 @@ constexpr int kBlock = 256;           // 4 waves of 64 lanes
 constexpr int kVec = 16;              // bytes per lane per shard
 constexpr int kTile = kBlock * kVec;  // 4 KiB column tile per workgroup step
 constexpr int kTbl = EC_TBL_DWORDS;
+
+// Work items of one launch at most: keeps w / tiles in 32-bit scalar math.
+// Launchers over more slice the stripes (for_slices).
+constexpr unsigned kMaxItems = 1u << 30;
+
+// f(s0, ns, ptrs) for every slice [s0, s0 + ns) of at most `per` stripes, ptrs
+// = the slice's rows of the pointer table; stops at f's first error.
+template <class F>
+hipError_t for_slices(const uint64_t* d_ptrs, int ptr_stride, long long nstripes, unsigned per, F&& f) {
+  for (long long s0 = 0; s0 < nstripes; s0 += per) {
+    const unsigned ns = static_cast<unsigned>(nstripes - s0 < per ? nstripes - s0 : per);
+    const hipError_t e = f(s0, ns, d_ptrs + s0 * ptr_stride);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
 
 struct Sel {
   uint32_t s0, s1, s2;
@@ -359,6 +376,35 @@ __device__ __forceinline__ void enc_fold_group(uint32_t (&acc)[P][4], const uint
   if constexpr (PAIR == 2 && ((U - U0) & 1)) {
     mac16<P, X, LT>(acc, x[U - 1], tbl + (j + U - 1) * P * kTbl, X ? r0_mask(r0m, j + U - 1) : 0u,
                     lt + (j + U - 1) * P);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// The fused encode+CRC kernels' fold (crc_kernels.hip, crc64_kernels.hip):
+// acc ^= the U sources x[] (sources j..j+U-1) times their coefficients, in
+// pairs while P <= 4; each source also goes to feed(source, chunk), which
+// advances its CRC chain. R0: row 0 is the 0/1 row x0src (mac16's R0).
+template <int P, int U, bool R0 = false, class Feed>
+__device__ __forceinline__ void mac_feed(uint32_t (&acc)[P][4], const uint4 (&x)[U], int j,
+                                         const uint32_t* __restrict__ tbl, const Feed& feed,
+                                         unsigned long long x0src = 0) {
+  constexpr int PAIR = P <= 4 ? 2 : 1;
+#pragma unroll
+  for (int u = 0; u + PAIR <= U; u += PAIR) {
+    if constexpr (PAIR == 2) {
+      mac16x2<P, R0>(acc, x[u], x[u + 1], tbl + (j + u) * P * kTbl, tbl + (j + u + 1) * P * kTbl,
+                     r0_mask(x0src, j + u), r0_mask(x0src, j + u + 1));
+      feed(j + u, x[u]);
+      feed(j + u + 1, x[u + 1]);
+    } else {
+      mac16<P, R0>(acc, x[u], tbl + (j + u) * P * kTbl, r0_mask(x0src, j + u));
+      feed(j + u, x[u]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  if constexpr (PAIR == 2 && (U & 1)) {
+    mac16<P, R0>(acc, x[U - 1], tbl + (j + U - 1) * P * kTbl, r0_mask(x0src, j + U - 1));
+    feed(j + U - 1, x[U - 1]);
     __builtin_amdgcn_sched_barrier(0);
   }
 }

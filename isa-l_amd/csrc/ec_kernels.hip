@@ -907,8 +907,6 @@ __global__ __launch_bounds__(kBlock) void ec_encode_karg_ldsx(const isal_hip_kar
 // ---------------------------------------------------------------------------
 // Host-side launch helpers
 // ---------------------------------------------------------------------------
-constexpr unsigned kMaxItems = 1u << 30;  // keep w / tiles in 32-bit scalar math
-
 unsigned tiles_of(int len, long long span) { return static_cast<unsigned>((len + span - 1) / span); }
 
 // Run-time value -> template argument: f(integral_constant<int, n>) for the n
@@ -1194,18 +1192,6 @@ unsigned stripes_per_launch(int len, bool vec16, long long vspan = kTile) {
   const long long tiles = (static_cast<long long>(len) + span - 1) / span;
   const long long n = static_cast<long long>(kMaxItems) / (tiles ? tiles : 1);
   return static_cast<unsigned>(n > 0 ? n : 1);
-}
-
-// f(s0, ns, ptrs) for every slice [s0, s0 + ns) of at most `per` stripes, ptrs
-// = the slice's rows of the pointer table; stops at f's first error.
-template <class F>
-hipError_t for_slices(const uint64_t* d_ptrs, int ptr_stride, long long nstripes, unsigned per, F&& f) {
-  for (long long s0 = 0; s0 < nstripes; s0 += per) {
-    const unsigned ns = static_cast<unsigned>(nstripes - s0 < per ? nstripes - s0 : per);
-    const hipError_t e = f(s0, ns, d_ptrs + s0 * ptr_stride);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
 }
 
 // The 0/1 masks of a call, or none under ISAL_HIP_ENC_XOR=0 (read at launch,

@@ -305,7 +305,7 @@ int isal_hip_launch_locate_batch(const uint64_t *d_ptrs, int ptr_stride, const u
 #define ISAL_HIP_RAGGED_TILE 4096
 #define ISAL_HIP_RAGGED_TILE_SMALL 2048
 #define ISAL_HIP_RAGGED_SMALL_ROWS 2
-#define ISAL_HIP_RAGGED_MAX_ITEMS (1u << 30) /* ec_kernels.hip kMaxItems */
+#define ISAL_HIP_RAGGED_MAX_ITEMS (1u << 30) /* ec_device.h kMaxItems */
 /* the item tables of an object, by tile size */
 enum { TILE_BIG, TILE_SMALL, NTILES };
 static inline int
@@ -527,6 +527,18 @@ typedef struct {
 #define ISAL_HIP_CRC_RAG_SQ_DWORDS 32 /* a wave's lanes 0..31 read one word each */
 #define ISAL_HIP_CRC_RAG_PW (ISAL_HIP_CRC_RAG_SQ + ISAL_HIP_CRC_RAG_SQ_DWORDS)
 #define ISAL_HIP_CRC_RAG_MAX_TT 1024 /* ISAL_HIP_CRC_TILES is clamped to this */
+/* What the first checksum call of one width allocates on a ragged object
+ * (isal_hip_ragged_crc.c): the block size it picked, the {stripe, block} item
+ * table with its per-stripe prefix first[], and the partials, one word of the
+ * width per (item, shard, lane). d_part != NULL: set up. */
+typedef struct {
+        int tt;
+        unsigned nitems;
+        unsigned *d_items, *d_first;
+        void *d_part;
+} isal_hip_ragged_ck;
+void isal_hip_ragged_ck_drop(isal_hip_ragged_ck *ck);
+
 /* The ragged batch object (isal_hip_ragged.c; its checksum state is
  * isal_hip_ragged_crc.c's). */
 struct isal_hip_ragged {
@@ -539,17 +551,11 @@ struct isal_hip_ragged {
         /* the checksums' own state (isal_hip_ragged_crc): the lengths as
          * create saw them, then what the first checksum call allocates */
         int *h_lens;
-        int crc_tt;
-        unsigned crc_nitems;
-        uint32_t *d_crc, *d_part, *d_tail;
-        unsigned *d_crc_items, *d_crc_first;
-        /* CRC64's own (isal_hip_ragged_crc64.c): block size, item tables and
-         * partials from its first call, one image per variant from the first
-         * call with that variant */
-        int c64_tt;
-        unsigned c64_nitems;
-        uint64_t *d_c64part;
-        unsigned *d_c64_items, *d_c64_first;
+        isal_hip_ragged_ck ck32;  /* CRC32C: its partials are followed by the tail rows, d_tail */
+        uint32_t *d_crc, *d_tail; /* CRC32C's image (set: CRC32C is set up) */
+        /* CRC64's own: block size, item table and partials from its first
+         * call, one image per variant from the first call with that variant */
+        isal_hip_ragged_ck ck64;
         uint64_t *d_c64image[8]; /* ISAL_HIP_CRC64_NVARIANTS */
         /* the sector checksums' own (isal_hip_sector_crc.c): one image per
          * flavour and one table of first sectors per sector size, each from the

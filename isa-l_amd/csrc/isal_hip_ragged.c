@@ -177,21 +177,28 @@ isal_hip_ragged_check(isal_hip_ragged *r, unsigned long long *bad, void *stream)
         ON_BATCH_DEVICE(r, ragged_check_impl(r, bad, stream));
 }
 
+/* Frees one width's checksum state (isal_hip_ragged_crc.c builds it, and
+ * rolls a failed set-up back with this) and leaves it as create did. */
+void
+isal_hip_ragged_ck_drop(isal_hip_ragged_ck *ck)
+{
+        isal_hip_obj_drop(ck->d_part);
+        isal_hip_obj_drop(ck->d_items);
+        isal_hip_obj_drop(ck->d_first);
+        memset(ck, 0, sizeof(*ck));
+}
+
 int
 isal_hip_ragged_destroy(isal_hip_ragged *r)
 {
         int t;
         if (!r)
                 return ISAL_HIP_OK;
-        /* what the first checksum call allocated (isal_hip_ragged_crc.c) */
+        /* what the first checksum calls of either width allocated
+         * (isal_hip_ragged_crc.c) */
         isal_hip_obj_drop(r->d_crc);
-        isal_hip_obj_drop(r->d_part);
-        isal_hip_obj_drop(r->d_crc_items);
-        isal_hip_obj_drop(r->d_crc_first);
-        /* ... and the first CRC64 calls (isal_hip_ragged_crc64.c) */
-        isal_hip_obj_drop(r->d_c64part);
-        isal_hip_obj_drop(r->d_c64_items);
-        isal_hip_obj_drop(r->d_c64_first);
+        isal_hip_ragged_ck_drop(&r->ck32);
+        isal_hip_ragged_ck_drop(&r->ck64);
         for (t = 0; t < (int) (sizeof(r->d_c64image) / sizeof(r->d_c64image[0])); t++)
                 isal_hip_obj_drop(r->d_c64image[t]);
         /* ... and the sector checksums (isal_hip_sector_crc.c) */

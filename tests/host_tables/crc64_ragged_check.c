@@ -91,7 +91,7 @@ dev_mulmod(int refl, uint64_t a, uint64_t b, uint64_t poly)
         return (uint64_t) ph << 32 | pl;
 }
 
-/* a map stored as 14 field tables (lookup14 / apply_op) */
+/* a map stored as 14 field tables (crc_device.h lookup14 / apply_op) */
 static uint64_t
 fields_op(const uint64_t *t, uint64_t v)
 {
@@ -104,7 +104,7 @@ fields_op(const uint64_t *t, uint64_t v)
         return r;
 }
 
-/* a chunk map stored as 28 field tables (chunk_acc) */
+/* a chunk map stored as 28 field tables (crc_device.h chunk_acc) */
 static uint64_t
 fields_chunk(const uint64_t *t, const uint32_t w[4])
 {

@@ -25,7 +25,7 @@ instantiation is reached through engine.Batch(...).encode_crc / .encode_crc64.
 Reaching a cell (REACH: cell -> (k, rows, form of parity row 0)); only
 ISAL_HIP_CRC_TILES and ISAL_HIP_LOG are set, the mapping is the library's own:
   * U is the largest of 12, 10, 8, 6, 5, 4 that divides k, else 4
-    (enc_group_crc, group_u);
+    (fused_group, crc_device.h);
   * X0 = 1 when parity row 0 is all 0/1 (isal_hip_xor_rows). The X0 = 1 cells
     use a 0/1 *mix* (ones at the first and the last source, at least one
     zero, so x0src is not all ones), the X0 = 0 cells a general row 0. All
@@ -91,7 +91,7 @@ pytestmark = pytest.mark.gpu
 
 CRC32C, CRC64 = "ec_encode_crc_v16", "ec_encode_crc64_v16"
 ROWS = tuple(range(1, 9))
-GROUPS = (12, 10, 8, 6, 5, 4)  # enc_group_crc's and group_u's candidates
+GROUPS = (12, 10, 8, 6, 5, 4)  # fused_group's candidates
 PIPELINED_ROWS = tuple(range(1, 5))  # CRC64, U = 10: SL = 3
 
 # the (SRC, X0, NB, NV) tails of ec_encode_crc_v16<P, U, ...>
@@ -129,7 +129,7 @@ GENERAL, MIX = "general", "mix"  # parity row 0: any bytes / a 0/1 mix
 
 
 def group_of(k):
-    """enc_group_crc / group_u."""
+    """fused_group (crc_device.h)."""
     for u in GROUPS:
         if k >= u and k % u == 0:
             return u
