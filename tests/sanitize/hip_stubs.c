@@ -6,7 +6,11 @@
  * drives; the weak ones here only fail. For stage_host.c, which links the
  * drop-in shim's staging routes and their context: streams, events,
  * page-locked memory and asynchronous copies, and the plain encode / update /
- * verify launchers as runs of the CPU route.
+ * verify launchers as runs of the CPU route. For pipe_host.c, which links the
+ * host pipeline and the multi-device encode: while g_hip_model is set (only
+ * that program sets it, hm_start) streams, events, device memory, asynchronous
+ * copies and the encode / update launchers go to the deferred model of
+ * hip_model.c instead of completing at once.
  */
 #include "hip_stubs.h"
 
@@ -17,6 +21,8 @@ static volatile unsigned char g_sink;
 hipError_t
 hipGetDevice(int *d)
 {
+        if (g_hip_model)
+                return hm_get_device(d);
         g_hip_calls++;
         *d = 0;
         return hipSuccess;
@@ -25,6 +31,8 @@ hipGetDevice(int *d)
 hipError_t
 hipMalloc(void **p, size_t n)
 {
+        if (g_hip_model)
+                return hm_malloc(p, n);
         g_hip_calls++;
         CHECK(n > 0);
         *p = malloc(n); /* exactly n: ASan guards the end of every table */
@@ -44,6 +52,8 @@ hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind kind)
 hipError_t
 hipFree(void *p)
 {
+        if (g_hip_model)
+                return hm_free(p);
         free(p);
         g_allocs--;
         return hipSuccess;
@@ -59,6 +69,8 @@ static char g_handle;
 hipError_t
 hipStreamCreate(hipStream_t *s)
 {
+        if (g_hip_model)
+                return hm_stream_create(s);
         *s = (hipStream_t) &g_handle;
         return hipSuccess;
 }
@@ -73,21 +85,25 @@ hipStreamCreateWithFlags(hipStream_t *s, unsigned flags)
 hipError_t
 hipStreamDestroy(hipStream_t s)
 {
-        (void) s;
+        if (g_hip_model)
+                return hm_stream_destroy(s);
         return hipSuccess;
 }
 
 hipError_t
 hipStreamSynchronize(hipStream_t s)
 {
-        (void) s;
+        if (g_hip_model)
+                return hm_stream_synchronize(s);
         return hipSuccess;
 }
 
 hipError_t
 hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned flags)
 {
-        (void) s, (void) e, (void) flags;
+        (void) flags;
+        if (g_hip_model)
+                return hm_stream_wait_event(s, e);
         return hipSuccess;
 }
 
@@ -95,6 +111,8 @@ hipError_t
 hipEventCreateWithFlags(hipEvent_t *e, unsigned flags)
 {
         (void) flags;
+        if (g_hip_model)
+                return hm_event_create(e);
         *e = (hipEvent_t) &g_handle;
         return hipSuccess;
 }
@@ -102,21 +120,24 @@ hipEventCreateWithFlags(hipEvent_t *e, unsigned flags)
 hipError_t
 hipEventDestroy(hipEvent_t e)
 {
-        (void) e;
+        if (g_hip_model)
+                return hm_event_destroy(e);
         return hipSuccess;
 }
 
 hipError_t
 hipEventRecord(hipEvent_t e, hipStream_t s)
 {
-        (void) e, (void) s;
+        if (g_hip_model)
+                return hm_event_record(e, s);
         return hipSuccess;
 }
 
 hipError_t
 hipEventSynchronize(hipEvent_t e)
 {
-        (void) e;
+        if (g_hip_model)
+                return hm_event_synchronize(e);
         return hipSuccess;
 }
 
@@ -146,8 +167,18 @@ hipHostGetDevicePointer(void **d, void *h, unsigned flags)
 hipError_t
 hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind kind, hipStream_t stream)
 {
-        (void) kind, (void) stream;
+        if (g_hip_model)
+                return hm_memcpy_async(d, s, n, kind, stream);
         memcpy(d, s, n);
+        return hipSuccess;
+}
+
+hipError_t
+hipMemsetAsync(void *d, int value, size_t n, hipStream_t stream)
+{
+        if (g_hip_model)
+                return hm_memset_async(d, value, n, stream);
+        memset(d, value, n);
         return hipSuccess;
 }
 
@@ -160,7 +191,25 @@ hipGetLastError(void)
 hipError_t
 hipSetDevice(int d)
 {
-        (void) d;
+        if (g_hip_model)
+                return hm_set_device(d);
+        return hipSuccess;
+}
+
+hipError_t
+hipGetDeviceCount(int *n)
+{
+        if (g_hip_model)
+                return hm_get_device_count(n);
+        *n = 1;
+        return hipSuccess;
+}
+
+/* a distinct bus id per device (none of them in any sysfs tree) */
+hipError_t
+hipDeviceGetPCIBusId(char *bus, int len, int dev)
+{
+        snprintf(bus, (size_t) len, "ffff:%02x:00.0", dev);
         return hipSuccess;
 }
 
@@ -193,13 +242,41 @@ plain_launch(int op, const uint64_t *d_ptrs, int src0, int nsrc, int dst0, const
         return key;
 }
 
+/* The same launch as an operation of the deferred model: its arguments now,
+ * the pointer table, the tables and the shards when its stream reaches it. */
+typedef struct {
+        int op, src0, nsrc, dst0, len, k, rows, vec_i, vec16;
+        const uint64_t *d_ptrs;
+        const uint32_t *d_tbl;
+} launch_args;
+
+static void
+launch_run(void *arg)
+{
+        const launch_args *a = arg;
+        (void) plain_launch(a->op, a->d_ptrs, a->src0, a->nsrc, a->dst0, a->d_tbl, a->len, a->k, a->rows, a->vec_i,
+                            a->vec16);
+}
+
+static void
+launch(void *stream, launch_args a)
+{
+        if (g_hip_model) {
+                launch_args *h = malloc(sizeof(*h));
+                CHECK(h);
+                *h = a;
+                hm_launch(stream, launch_run, h);
+        } else
+                launch_run(&a);
+}
+
 int
 isal_hip_launch_encode(const uint64_t *d_ptrs, int ptr_stride, int src_idx0, int dst_idx0, const uint32_t *d_tbl,
                        int len, int k, int rows, long long nstripes, int vec16, const isal_hip_encmask *em,
                        void *stream)
 {
         CHECK(nstripes == 1 && ptr_stride >= k + rows);
-        (void) plain_launch(ISAL_HIP_OP_ENCODE, d_ptrs, src_idx0, k, dst_idx0, d_tbl, len, k, rows, 0, vec16);
+        launch(stream, (launch_args) {ISAL_HIP_OP_ENCODE, src_idx0, k, dst_idx0, len, k, rows, 0, vec16, d_ptrs, d_tbl});
         return 0;
 }
 
@@ -208,7 +285,7 @@ isal_hip_launch_update(const uint64_t *d_ptrs, int ptr_stride, int src_idx, int 
                        int len, int k, int rows, int vec_i, long long nstripes, int vec16, void *stream)
 {
         CHECK(nstripes == 1 && ptr_stride >= 1 + rows);
-        (void) plain_launch(ISAL_HIP_OP_UPDATE, d_ptrs, src_idx, 1, dst_idx0, d_tbl, len, k, rows, vec_i, vec16);
+        launch(stream, (launch_args) {ISAL_HIP_OP_UPDATE, src_idx, 1, dst_idx0, len, k, rows, vec_i, vec16, d_ptrs, d_tbl});
         return 0;
 }
 
@@ -229,14 +306,21 @@ isal_hip_launch_verify(const uint64_t *d_ptrs, int ptr_stride, int src_idx0, int
 int
 isal_hip_dev_enter(int dev)
 {
-        (void) dev;
+        int cur;
+        if (g_hip_model) { /* as the engine's own: the device to restore, -1 when none */
+                (void) hm_get_device(&cur);
+                if (cur == dev)
+                        return -1;
+                return hm_set_device(dev) == hipSuccess ? cur : -2;
+        }
         return -1;
 }
 
 void
 isal_hip_dev_leave(int prev)
 {
-        (void) prev;
+        if (g_hip_model && prev >= 0)
+                (void) hm_set_device(prev);
 }
 
 /* Never over no bytes (zero-length stripes are not classified), and over the

@@ -47,9 +47,11 @@ def test_abi_edges_under_asan_ubsan(sanitized_builds):
 # the stripe objects' host sources on a stubbed HIP runtime (tests/sanitize/
 # hip_stubs.c): every create's refusals and uploaded tables, stand-alone; and
 # (stage_host) the drop-in shim's staging routes: every route, whole and after
-# each injected fault, completed on the CPU route
+# each injected fault, completed on the CPU route; and (pipe_host) the host
+# pipeline and the multi-device encode on a deferred model of HIP streams
+# (hip_model.c), under all six priority orders of its three streams
 HOST_PROGRAMS = ["overwrite_host", "overwrite_ragged_host", "ragged_host", "repair_host", "repair_ragged_host",
-                 "scrub_host", "scrub_ragged_host", "stage_host"]
+                 "scrub_host", "scrub_ragged_host", "stage_host", "pipe_host"]
 
 
 @pytest.mark.parametrize("name", HOST_PROGRAMS)
