@@ -703,11 +703,11 @@ int isal_hip_ragged_destroy(isal_hip_ragged *r);
  *   bytes per stripe); the ragged work items are the encode's 4 KiB {stripe,
  *   tile} table. A failed allocation returns ISAL_HIP_ENOMEM or ISAL_HIP_EHIP,
  *   leaves no HIP error behind and the object as usable as before.
- * Out of scope: sectors below 512 B or above one 4 KiB tile; CRC16 T10-DIF,
- * the 16-bit NVMe guard (a new polynomial's tables and the rest of crc.h: the
- * natural follow-up); fusing into the encode pass; comparing against stored
- * checksums on the device; unaligned or host-pageable shards; any CPU route;
- * the drop-in ABI.
+ * Out of scope: sectors below 512 B or above one 4 KiB tile; the rest of crc.h
+ * (crc32_ieee, crc32_gzip_refl); fusing into the encode pass; unaligned or
+ * host-pageable shards; any CPU route; the drop-in ABI. (The 16-bit guard and
+ * the comparison with stored checksums on the device: "T10 protection
+ * information" below.)
  */
 int isal_hip_batch_sector_crc(isal_hip_batch *b, int sector, unsigned int init, unsigned int *crc,
                               void *stream);
@@ -718,6 +718,87 @@ int isal_hip_ragged_sector_crc(isal_hip_ragged *r, int sector, unsigned int init
                                void *stream);
 int isal_hip_ragged_sector_crc64(isal_hip_ragged *r, int variant, int sector, unsigned long long init,
                                  unsigned long long *crc, void *stream);
+
+/* ---- T10 protection information: guard, generate and verify per sector ---- */
+
+/*
+ * The 8-byte tuple that T10 DIF types 1-3 and NVMe protection information with
+ * the 16-bit guard keep per logical block, in the DIX layout (the tuples in an
+ * array of their own, not interleaved with the data):
+ *   bytes 0-1  guard: crc16_t10dif of the sector's bytes (the reference's
+ *              crc16_t10dif(seed, p, n): a normal CRC, polynomial x^16 +
+ *              0x8BB7, the register starts at seed, no final XOR; "123456789"
+ *              from 0 gives 0xD0DB)
+ *   bytes 2-3  application tag
+ *   bytes 4-7  reference tag: ref0 of the shard for ISAL_HIP_DIF_TYPE3, ref0 +
+ *              i (mod 2^32) for sector i under ISAL_HIP_DIF_TYPE1 (also type 2)
+ * each field most significant byte first. Sectors, their indexing and a short
+ * last sector (its guard covers the bytes that exist) are the sector
+ * checksums' above: word or tuple (s*m + j)*ns + i on the uniform batch,
+ * m*first[s] + j*ns_s + i on the ragged one (isal_hip_ragged_sector_offsets).
+ * All arrays are DEVICE memory:
+ *   crc   one 16-bit word per sector
+ *   pi    8 bytes per sector, 8-byte aligned
+ *   bad, d->ref0   one 32-bit word per shard, at s*m + j (ref0 NULL: all 0)
+ *   _sector_t10dif  crc[w] = the guard, with the same seed for every sector.
+ *   _dif_generate   pi[8w .. 8w+8) = the tuple (d->seed, d->app_tag, d->type,
+ *                   d->ref0; d->flags is not looked at).
+ *   _dif_verify     compares the stored tuple of every sector with the one
+ *                   generate would write, in the fields d->flags names
+ *                   (ISAL_HIP_DIF_CHECK_*). bad[s*m + j] = ISAL_HIP_DIF_CLEAN
+ *                   when no sector of the shard fails, else (i << 3) | kinds
+ *                   for the FIRST failing sector i, kinds the OR of the
+ *                   CHECK_* bits that failed in that sector. Escape rule: a
+ *                   sector is not checked at all when its stored application
+ *                   tag is 0xFFFF (type 1) or its stored application tag is
+ *                   0xFFFF and its stored reference tag 0xFFFFFFFF (type 3).
+ *                   Unlike the scrub's verdict (at most ONE shard per stripe,
+ *                   from the syndrome) this names every bad shard, up to the
+ *                   m - k a repair can take, and the sector to start at: the
+ *                   erasure list of isal_hip_repair_create[_ragged].
+ * Refusals (ISAL_HIP_EINVAL before any HIP call, nothing enqueued), object
+ * behaviour and device routing are the sector checksums': a NULL object, d,
+ * crc, pi or bad, a bad sector, a type other than the two above, flags outside
+ * the three bits, a pi not 8-byte aligned, unaligned shards on the uniform
+ * batch, more than 2^30 work items. With every length 0 a call returns 0,
+ * enqueues nothing and writes nothing (bad included). The words and generate
+ * enqueue exactly ONE kernel launch; verify enqueues a fill of bad with 0xff
+ * bytes and then ONE kernel launch, whose only writes are atomic minima of
+ * failing sectors (a clean batch issues none). Stream-ordered on the caller's
+ * stream, on the object's device, idempotent. The first call uploads the
+ * guard's tables (7 KiB, freed by the object's destroy); a failed upload
+ * returns ISAL_HIP_ENOMEM or ISAL_HIP_EHIP and leaves no HIP error behind.
+ * Out of scope: the drop-in symbols crc16_t10dif[_copy][_base] and a
+ * whole-shard CRC-16; crc32_ieee, crc32_gzip_refl; application-tag masks; the
+ * 32- and 64-bit NVMe guards as tuples; fusing into the encode pass; any CPU
+ * route; interleaved data + PI (DIF proper).
+ */
+#define ISAL_HIP_DIF_TYPE1 1          /* also type 2: ref tag of sector i = ref0 + i (mod 2^32) */
+#define ISAL_HIP_DIF_TYPE3 3          /* ref tag = ref0 for every sector of the shard */
+#define ISAL_HIP_DIF_CHECK_GUARD 1u   /* also the bit of `kinds` in a verify word */
+#define ISAL_HIP_DIF_CHECK_APP   2u
+#define ISAL_HIP_DIF_CHECK_REF   4u
+#define ISAL_HIP_DIF_CLEAN 0xffffffffu
+typedef struct {
+        int type;
+        unsigned flags;               /* verify only */
+        unsigned short app_tag;
+        unsigned short seed;          /* crc16 seed, normally 0 */
+        const unsigned int *ref0;     /* DEVICE, one word per shard in pi order; NULL: all 0 */
+} isal_hip_dif;
+
+int isal_hip_batch_sector_t10dif(isal_hip_batch *b, int sector, unsigned short seed, unsigned short *crc,
+                                 void *stream);
+int isal_hip_ragged_sector_t10dif(isal_hip_ragged *r, int sector, unsigned short seed, unsigned short *crc,
+                                  void *stream);
+int isal_hip_batch_dif_generate(isal_hip_batch *b, int sector, const isal_hip_dif *d, unsigned char *pi,
+                                void *stream);
+int isal_hip_ragged_dif_generate(isal_hip_ragged *r, int sector, const isal_hip_dif *d, unsigned char *pi,
+                                 void *stream);
+int isal_hip_batch_dif_verify(isal_hip_batch *b, int sector, const isal_hip_dif *d, const unsigned char *pi,
+                              unsigned int *bad, void *stream);
+int isal_hip_ragged_dif_verify(isal_hip_ragged *r, int sector, const isal_hip_dif *d, const unsigned char *pi,
+                               unsigned int *bad, void *stream);
 
 /* ---- streaming pipeline for HOST-resident stripes ----------------------- */
 

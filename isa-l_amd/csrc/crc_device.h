@@ -1,6 +1,6 @@
 // crc_device.h — device-side building blocks shared by the checksum kernels:
 // crc_kernels.hip (CRC32C), crc64_kernels.hip (the crc64_* flavours) and
-// crc_sector_kernels.hip (both, per sector). One definition each of the chunk
+// crc_sector_kernels.hip (both and the 16-bit T10 guard, per sector). One definition each of the chunk
 // path of either width — field offsets, the conflict-free table lookups, the
 // chunk and chain maps — and of what the kernels of both widths do alike: a
 // block's tile range, the byte offsets of the fused kernels' byte tables, the
@@ -60,6 +60,20 @@ __device__ __forceinline__ uint32_t chunk_map(const uint32_t* t, uint32_t w0, ui
                                               uint32_t w2, uint32_t w3) {
   constexpr int D = kF * 32;  // tables per dword of the chunk
   return xor3(lookup7(t, w0), lookup7(t + D, w1), lookup7(t + 2 * D, w2)) ^ lookup7(t + 3 * D, w3);
+}
+
+// ---- crc16: a 16-bit register through CRC32C's dword tables -------------------
+// XOR of the 4 field lookups of the 16-bit w (bits [0,5) [5,10) [10,15)
+// [15,16); the bits above are 0) in the 4 consecutive 32-entry tables at t:
+// field_offsets4 without the three offsets a 16-bit value does not have.
+__device__ __forceinline__ uint32_t lookup4(const uint32_t* t, uint32_t w) {
+  const uint32_t s = w << 2;
+  const uint32_t ev = s & 0x0001F07Cu;  // fields 0, 2 at [2,7) [12,17)
+  const uint32_t od = s & 0x00020F80u;  // fields 1, 3 at [7,12) [17,18)
+  const uint32_t o0 = ev & 0x7Cu, o1 = bfe<5, 7>(od), o2 = bfe<10, 7>(ev), o3 = bfe<15, 7>(od);
+  const char* b = reinterpret_cast<const char*>(t);
+  auto at = [&](int f, uint32_t o) { return *reinterpret_cast<const uint32_t*>(b + f * 128 + o); };
+  return xor3(at(0, o0), at(1, o1), at(2, o2)) ^ at(3, o3);
 }
 
 // ---- crc64: 32-entry qword tables -------------------------------------------

@@ -261,6 +261,7 @@ isal_hip_batch_destroy(isal_hip_batch *b)
         isal_hip_obj_drop(b->d_sec32);
         for (int v = 0; v < ISAL_HIP_CRC64_NVARIANTS; v++)
                 isal_hip_obj_drop(b->d_sec64[v]);
+        isal_hip_obj_drop(b->d_sec16); /* ... and the T10 guard's (isal_hip_dif.c) */
         free(b);
         return ISAL_HIP_OK;
 }

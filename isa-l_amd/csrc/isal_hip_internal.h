@@ -563,6 +563,7 @@ struct isal_hip_ragged {
         uint32_t *d_sec32;
         uint64_t *d_sec64[8];
         unsigned long long *d_sec_first[4]; /* ISAL_HIP_SECTOR_NSIZES */
+        uint32_t *d_sec16; /* the T10 guard's image (isal_hip_dif.c), from its first call */
 };
 /* isal_hip_ragged_encode's body, for a caller already on the object's device */
 int isal_hip_ragged_encode_on_device(struct isal_hip_ragged *r, void *stream);
@@ -790,6 +791,57 @@ int isal_hip_launch_sector_crc32c(const isal_hip_sector_geom *g, const uint32_t 
                                   uint32_t *out, void *stream);
 int isal_hip_launch_sector_crc64(const isal_hip_sector_geom *g, const uint64_t *d_image, int refl, uint64_t poly,
                                  uint64_t init, uint64_t *out, void *stream);
+/* What the entry points of isal_hip_sector_crc.c and isal_hip_dif.c share; no
+ * HIP call unless stated.
+ * _batch_geom / _ragged_geom: ISAL_HIP_EINVAL for a NULL object, a bad sector,
+ *   (uniform) an unaligned shard or more work items than one launch takes; 1
+ *   when every length is 0 (nothing to do); else 0 with *g filled but for
+ *   d_first, which isal_hip_sector_ragged_first uploads at the first call with
+ *   that sector size (on the object's device) and sets.
+ * _put: *slot = the device copy of the malloc'ed image h (freed here; NULL:
+ *   ISAL_HIP_ENOMEM); a failure leaves *slot NULL and no HIP error behind. */
+struct isal_hip_batch;
+int isal_hip_sector_index(int sector);
+int isal_hip_sector_batch_geom(const struct isal_hip_batch *b, int sector, isal_hip_sector_geom *g);
+int isal_hip_sector_ragged_geom(const struct isal_hip_ragged *r, int sector, isal_hip_sector_geom *g);
+int isal_hip_sector_ragged_first(struct isal_hip_ragged *r, int sector, isal_hip_sector_geom *g);
+int isal_hip_sector_put(void *slot, void *h, size_t bytes);
+
+/* ---- T10 protection information (isal_hip_dif.c, crc_sector_kernels.hip) ----
+ * The sector pass over a third family, crc16_t10dif: a normal (not reflected)
+ * 16-bit register in the low half of a dword, polynomial x^16 + 0x8BB7, bit i
+ * the coefficient of x^i. Its image: the chunk map in the layout of CHUNK_TAB
+ * (28 field tables of 32 dwords), then for each Z^(16 * 2^d), d = 0 ..
+ * ISAL_HIP_SECTOR_NZ - 1, the ISAL_HIP_CRC16_FIELDS field tables of a 16-bit
+ * register: bits [0,5) [5,10) [10,15) [15,16). */
+#define ISAL_HIP_CRC16_POLY 0x8BB7u
+#define ISAL_HIP_CRC16_FIELDS 4
+#define ISAL_HIP_CRC16_OP_DWORDS (ISAL_HIP_CRC16_FIELDS * 32)
+#define ISAL_HIP_SECTOR16_DWORDS (ISAL_HIP_CRC_CHUNK_DWORDS + ISAL_HIP_SECTOR_NZ * ISAL_HIP_CRC16_OP_DWORDS)
+uint32_t isal_hip_crc16_mulmod(uint32_t a, uint32_t b);
+uint32_t isal_hip_crc16_xpow8n(unsigned long long n); /* x^(8n) mod P */
+void isal_hip_crc16_sector_image(uint32_t *out);
+/* What the lane at position 0 of a sector does with its guard g (sector i of
+ * shard n = s*m + j, word w of the sector layout):
+ *   GUARD     crc[w] = g
+ *   GENERATE  the 8 bytes at pi + 8*w = g, app, ref, each most significant
+ *             byte first; ref = ref0[n] (0 for a NULL ref0), plus i for type 1
+ *   VERIFY    the stored tuple at pi + 8*w against g, app and ref under flags
+ *             and the escape rule (isal_hip.h); a failing sector does
+ *             atomicMin(bad + n, i << 3 | kinds). */
+enum { ISAL_HIP_DIF_GUARD, ISAL_HIP_DIF_GENERATE, ISAL_HIP_DIF_VERIFY };
+typedef struct {
+        int mode, type;
+        unsigned seed, app, flags;
+        const unsigned *ref0;
+        unsigned short *crc; /* GUARD */
+        unsigned char *pi;   /* GENERATE (written), VERIFY (read) */
+        unsigned *bad;       /* VERIFY */
+} isal_hip_dif_args;
+/* One launch, no other (the caller fills bad): hipErrorInvalidValue, nothing
+ * enqueued, as for isal_hip_launch_sector_crc32c or for an unknown mode. */
+int isal_hip_launch_sector_t10dif(const isal_hip_sector_geom *g, const uint32_t *d_image,
+                                  const isal_hip_dif_args *a, void *stream);
 
 /* The uniform batch object (isal_hip_batch.c; its sector checksums are
  * isal_hip_sector_crc.c's). */
@@ -815,6 +867,7 @@ struct isal_hip_batch {
         /* the sector checksums' images, from the first call that needs one */
         uint32_t *d_sec32;
         uint64_t *d_sec64[8];
+        uint32_t *d_sec16; /* the T10 guard's image (isal_hip_dif.c), from its first call */
 };
 
 #ifdef __cplusplus

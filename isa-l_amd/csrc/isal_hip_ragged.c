@@ -207,6 +207,7 @@ isal_hip_ragged_destroy(isal_hip_ragged *r)
                 isal_hip_obj_drop(r->d_sec64[t]);
         for (t = 0; t < ISAL_HIP_SECTOR_NSIZES; t++)
                 isal_hip_obj_drop(r->d_sec_first[t]);
+        isal_hip_obj_drop(r->d_sec16); /* ... and the T10 guard's (isal_hip_dif.c) */
         free(r->h_lens);
         isal_hip_obj_drop(r->d_ptrs);
         isal_hip_obj_drop(r->d_tbl);

@@ -26,8 +26,8 @@ _Static_assert(sizeof(((isal_hip_ragged *) 0)->d_sec_first) / sizeof(unsigned lo
                "one table of first sectors per sector size");
 
 /* index of a sector size among the ISAL_HIP_SECTOR_NSIZES allowed, or -1 */
-static int
-sector_index(int sector)
+int
+isal_hip_sector_index(int sector)
 {
         int i;
         for (i = 0; i < ISAL_HIP_SECTOR_NSIZES; i++)
@@ -41,7 +41,7 @@ isal_hip_ragged_sector_offsets(int nstripes, const int *lens, int sector, long l
 {
         long long n = 0;
         int s;
-        if (!lens || nstripes <= 0 || sector_index(sector) < 0)
+        if (!lens || nstripes <= 0 || isal_hip_sector_index(sector) < 0)
                 return -1;
         for (s = 0; s < nstripes; s++)
                 if (lens[s] < 0)
@@ -54,10 +54,11 @@ isal_hip_ragged_sector_offsets(int nstripes, const int *lens, int sector, long l
         return n;
 }
 
-/* *slot = the device copy of a freshly built image, unless it is there already.
- * A failure leaves *slot NULL and no HIP error behind. */
-static int
-sector_put(void *slot, void *h, size_t bytes)
+/* *slot = the device copy of a freshly built image (the callers look first
+ * whether it is there already). A failure leaves *slot NULL and no HIP error
+ * behind. */
+int
+isal_hip_sector_put(void *slot, void *h, size_t bytes)
 {
         void *d = NULL;
         int e;
@@ -83,7 +84,7 @@ sector_image32(uint32_t **slot)
         h = (uint32_t *) malloc((size_t) ISAL_HIP_SECTOR32_DWORDS * 4);
         if (h)
                 isal_hip_crc32c_sector_image(h);
-        return sector_put(slot, h, (size_t) ISAL_HIP_SECTOR32_DWORDS * 4);
+        return isal_hip_sector_put(slot, h, (size_t) ISAL_HIP_SECTOR32_DWORDS * 4);
 }
 
 static int
@@ -95,7 +96,7 @@ sector_image64(uint64_t **slot, int variant)
         h = (uint64_t *) malloc((size_t) ISAL_HIP_SECTOR64_ENTRIES * 8);
         if (h)
                 isal_hip_crc64_sector_image(variant, h);
-        return sector_put(slot, h, (size_t) ISAL_HIP_SECTOR64_ENTRIES * 8);
+        return isal_hip_sector_put(slot, h, (size_t) ISAL_HIP_SECTOR64_ENTRIES * 8);
 }
 
 /* variant < 0: CRC32C */
@@ -119,29 +120,28 @@ batch_tiles(const isal_hip_batch *b)
 }
 
 static int
-batch_sector_impl(isal_hip_batch *b, int variant, int sector, unsigned long long init, void *crc, void *stream)
+batch_sector_impl(isal_hip_batch *b, const isal_hip_sector_geom *g, int variant, unsigned long long init, void *crc,
+                  void *stream)
 {
-        isal_hip_sector_geom g = { 0 };
-        int e = variant < 0 ? sector_image32(&b->d_sec32) : sector_image64(&b->d_sec64[variant], variant);
+        const int e = variant < 0 ? sector_image32(&b->d_sec32) : sector_image64(&b->d_sec64[variant], variant);
         if (e != ISAL_HIP_OK)
                 return e;
-        g.d_ptrs = b->d_ptrs;
-        g.nsh = b->k + b->rows;
-        g.sector = sector;
-        g.len = b->len;
-        g.ntiles = (unsigned) batch_tiles(b);
-        g.nwork = (unsigned long long) b->nstripes * (unsigned long long) g.nsh * g.ntiles;
-        return sector_launch(&g, variant, b->d_sec32, variant < 0 ? NULL : b->d_sec64[variant], init, crc, stream);
+        return sector_launch(g, variant, b->d_sec32, variant < 0 ? NULL : b->d_sec64[variant], init, crc, stream);
 }
 
-/* what both uniform entry points refuse, before any HIP call; 1: nothing to do */
-static int
-batch_sector_check(const isal_hip_batch *b, int sector, const void *crc)
+/* what every uniform entry point refuses, before any HIP call; 1: nothing to do */
+int
+isal_hip_sector_batch_geom(const isal_hip_batch *b, int sector, isal_hip_sector_geom *g)
 {
-        if (!b || !crc || sector_index(sector) < 0 || !b->vec16)
+        if (!b || isal_hip_sector_index(sector) < 0 || !b->vec16)
                 return ISAL_HIP_EINVAL;
-        if ((unsigned long long) b->nstripes * (unsigned long long) (b->k + b->rows) * batch_tiles(b) >
-            (unsigned long long) ISAL_HIP_RAGGED_MAX_ITEMS)
+        g->d_ptrs = b->d_ptrs;
+        g->nsh = b->k + b->rows;
+        g->sector = sector;
+        g->len = b->len;
+        g->ntiles = (unsigned) batch_tiles(b);
+        g->nwork = (unsigned long long) b->nstripes * (unsigned long long) g->nsh * batch_tiles(b);
+        if (g->nwork > (unsigned long long) ISAL_HIP_RAGGED_MAX_ITEMS)
                 return ISAL_HIP_EINVAL;
         return b->len == 0;
 }
@@ -149,65 +149,68 @@ batch_sector_check(const isal_hip_batch *b, int sector, const void *crc)
 int
 isal_hip_batch_sector_crc(isal_hip_batch *b, int sector, unsigned int init, unsigned int *crc, void *stream)
 {
-        const int e = batch_sector_check(b, sector, crc);
+        isal_hip_sector_geom g = { 0 };
+        const int e = crc ? isal_hip_sector_batch_geom(b, sector, &g) : ISAL_HIP_EINVAL;
         if (e)
                 return e < 0 ? e : ISAL_HIP_OK;
-        ON_BATCH_DEVICE(b, batch_sector_impl(b, -1, sector, init, crc, stream));
+        ON_BATCH_DEVICE(b, batch_sector_impl(b, &g, -1, init, crc, stream));
 }
 
 int
 isal_hip_batch_sector_crc64(isal_hip_batch *b, int variant, int sector, unsigned long long init,
                             unsigned long long *crc, void *stream)
 {
+        isal_hip_sector_geom g = { 0 };
         int e;
-        if (variant < 0 || variant >= ISAL_HIP_CRC64_NVARIANTS)
+        if (variant < 0 || variant >= ISAL_HIP_CRC64_NVARIANTS || !crc)
                 return ISAL_HIP_EINVAL;
-        if ((e = batch_sector_check(b, sector, crc)) != 0)
+        if ((e = isal_hip_sector_batch_geom(b, sector, &g)) != 0)
                 return e < 0 ? e : ISAL_HIP_OK;
-        ON_BATCH_DEVICE(b, batch_sector_impl(b, variant, sector, init, crc, stream));
+        ON_BATCH_DEVICE(b, batch_sector_impl(b, &g, variant, init, crc, stream));
 }
 
 /* ---- the ragged batch ------------------------------------------------------- */
 
 /* first[s] of isal_hip_ragged_sector_offsets for this sector size, on the device */
-static int
-ragged_sector_first(isal_hip_ragged *r, int sector)
+int
+isal_hip_sector_ragged_first(isal_hip_ragged *r, int sector, isal_hip_sector_geom *g)
 {
-        unsigned long long **slot = &r->d_sec_first[sector_index(sector)];
-        long long *h;
-        if (*slot)
-                return ISAL_HIP_OK;
-        h = (long long *) malloc((size_t) r->nstripes * sizeof(long long));
-        if (h)
-                (void) isal_hip_ragged_sector_offsets(r->nstripes, r->h_lens, sector, h);
-        return sector_put(slot, h, (size_t) r->nstripes * sizeof(long long));
+        unsigned long long **slot = &r->d_sec_first[isal_hip_sector_index(sector)];
+        if (!*slot) {
+                long long *h = (long long *) malloc((size_t) r->nstripes * sizeof(long long));
+                int e;
+                if (h)
+                        (void) isal_hip_ragged_sector_offsets(r->nstripes, r->h_lens, sector, h);
+                if ((e = isal_hip_sector_put(slot, h, (size_t) r->nstripes * sizeof(long long))) != ISAL_HIP_OK)
+                        return e;
+        }
+        g->d_first = *slot;
+        return ISAL_HIP_OK;
 }
 
 static int
-ragged_sector_impl(isal_hip_ragged *r, int variant, int sector, unsigned long long init, void *crc, void *stream)
+ragged_sector_impl(isal_hip_ragged *r, isal_hip_sector_geom *g, int variant, unsigned long long init, void *crc,
+                   void *stream)
 {
-        isal_hip_sector_geom g = { 0 };
         int e;
-        if ((e = ragged_sector_first(r, sector)) != ISAL_HIP_OK ||
+        if ((e = isal_hip_sector_ragged_first(r, g->sector, g)) != ISAL_HIP_OK ||
             (e = variant < 0 ? sector_image32(&r->d_sec32) : sector_image64(&r->d_sec64[variant], variant)) != ISAL_HIP_OK)
                 return e;
-        g.d_ptrs = r->d_ptrs;
-        g.nsh = r->k + r->rows;
-        g.sector = sector;
-        g.d_lens = r->d_lens;
-        g.d_items = r->d_items[TILE_BIG]; /* the encode's 4 KiB {stripe, tile} table */
-        g.d_first = r->d_sec_first[sector_index(sector)];
-        g.nwork = (unsigned long long) r->nitems[TILE_BIG] * (unsigned long long) g.nsh;
-        return sector_launch(&g, variant, r->d_sec32, variant < 0 ? NULL : r->d_sec64[variant], init, crc, stream);
+        return sector_launch(g, variant, r->d_sec32, variant < 0 ? NULL : r->d_sec64[variant], init, crc, stream);
 }
 
-static int
-ragged_sector_check(const isal_hip_ragged *r, int sector, const void *crc)
+int
+isal_hip_sector_ragged_geom(const isal_hip_ragged *r, int sector, isal_hip_sector_geom *g)
 {
-        if (!r || !crc || sector_index(sector) < 0)
+        if (!r || isal_hip_sector_index(sector) < 0)
                 return ISAL_HIP_EINVAL;
-        if ((unsigned long long) r->nitems[TILE_BIG] * (unsigned long long) (r->k + r->rows) >
-            (unsigned long long) ISAL_HIP_RAGGED_MAX_ITEMS)
+        g->d_ptrs = r->d_ptrs;
+        g->nsh = r->k + r->rows;
+        g->sector = sector;
+        g->d_lens = r->d_lens;
+        g->d_items = r->d_items[TILE_BIG]; /* the encode's 4 KiB {stripe, tile} table */
+        g->nwork = (unsigned long long) r->nitems[TILE_BIG] * (unsigned long long) g->nsh;
+        if (g->nwork > (unsigned long long) ISAL_HIP_RAGGED_MAX_ITEMS)
                 return ISAL_HIP_EINVAL;
         return r->nitems[TILE_BIG] == 0; /* every length is 0 */
 }
@@ -215,20 +218,22 @@ ragged_sector_check(const isal_hip_ragged *r, int sector, const void *crc)
 int
 isal_hip_ragged_sector_crc(isal_hip_ragged *r, int sector, unsigned int init, unsigned int *crc, void *stream)
 {
-        const int e = ragged_sector_check(r, sector, crc);
+        isal_hip_sector_geom g = { 0 };
+        const int e = crc ? isal_hip_sector_ragged_geom(r, sector, &g) : ISAL_HIP_EINVAL;
         if (e)
                 return e < 0 ? e : ISAL_HIP_OK;
-        ON_BATCH_DEVICE(r, ragged_sector_impl(r, -1, sector, init, crc, stream));
+        ON_BATCH_DEVICE(r, ragged_sector_impl(r, &g, -1, init, crc, stream));
 }
 
 int
 isal_hip_ragged_sector_crc64(isal_hip_ragged *r, int variant, int sector, unsigned long long init,
                              unsigned long long *crc, void *stream)
 {
+        isal_hip_sector_geom g = { 0 };
         int e;
-        if (variant < 0 || variant >= ISAL_HIP_CRC64_NVARIANTS)
+        if (variant < 0 || variant >= ISAL_HIP_CRC64_NVARIANTS || !crc)
                 return ISAL_HIP_EINVAL;
-        if ((e = ragged_sector_check(r, sector, crc)) != 0)
+        if ((e = isal_hip_sector_ragged_geom(r, sector, &g)) != 0)
                 return e < 0 ? e : ISAL_HIP_OK;
-        ON_BATCH_DEVICE(r, ragged_sector_impl(r, variant, sector, init, crc, stream));
+        ON_BATCH_DEVICE(r, ragged_sector_impl(r, &g, variant, init, crc, stream));
 }

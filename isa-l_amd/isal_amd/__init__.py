@@ -30,6 +30,7 @@ __all__ = [
     "locate_syndrome", "SCRUB_CLEAN", "SCRUB_MULTI", "Ragged", "ragged_items", "ragged_sector_offsets", "Pipe", "kernel_launches", "max_rows_per_pass",
     "version", "addr", "cpu_calls", "fallbacks", "reload_config", "Multi", "partition",
     "route_device", "contexts_created", "selftest_kernels", "crc32_iscsi", "crc64", "CRC64_VARIANTS", "slow_waits",
+    "DIF_TYPE1", "DIF_TYPE3", "DIF_CHECK_GUARD", "DIF_CHECK_APP", "DIF_CHECK_REF", "DIF_CHECK_ALL", "DIF_CLEAN",
 ]
 
 LIB_PATH = os.environ.get(
@@ -151,6 +152,14 @@ def lib() -> ctypes.CDLL:
             "isal_hip_ragged_sector_crc": (i, [ctypes.c_void_p, i, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]),
             "isal_hip_ragged_sector_crc64": (i, [ctypes.c_void_p, i, i, ctypes.c_ulonglong, ctypes.c_void_p,
                                                  ctypes.c_void_p]),
+            "isal_hip_batch_sector_t10dif": (i, [ctypes.c_void_p, i, ctypes.c_ushort, ctypes.c_void_p, ctypes.c_void_p]),
+            "isal_hip_ragged_sector_t10dif": (i, [ctypes.c_void_p, i, ctypes.c_ushort, ctypes.c_void_p, ctypes.c_void_p]),
+            "isal_hip_batch_dif_generate": (i, [ctypes.c_void_p, i, ctypes.POINTER(_Dif), ctypes.c_void_p, ctypes.c_void_p]),
+            "isal_hip_ragged_dif_generate": (i, [ctypes.c_void_p, i, ctypes.POINTER(_Dif), ctypes.c_void_p, ctypes.c_void_p]),
+            "isal_hip_batch_dif_verify": (i, [ctypes.c_void_p, i, ctypes.POINTER(_Dif), ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p]),
+            "isal_hip_ragged_dif_verify": (i, [ctypes.c_void_p, i, ctypes.POINTER(_Dif), ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p]),
             "isal_hip_pipe_create": (i, [ctypes.POINTER(ctypes.c_void_p), i, i, i, _u8p, i, i]),
             "isal_hip_pipe_submit": (i, [ctypes.c_void_p, _u8pp, _u8pp]),
             "isal_hip_pipe_flush": (i, [ctypes.c_void_p]),
@@ -193,6 +202,35 @@ def lib() -> ctypes.CDLL:
 # ---------------------------------------------------------------------------
 # buffer plumbing
 # ---------------------------------------------------------------------------
+
+# T10 protection information (isal_hip.h ISAL_HIP_DIF_*)
+DIF_TYPE1, DIF_TYPE3 = 1, 3
+DIF_CHECK_GUARD, DIF_CHECK_APP, DIF_CHECK_REF, DIF_CHECK_ALL = 1, 2, 4, 7
+DIF_CLEAN = 0xFFFFFFFF
+
+
+class _Dif(ctypes.Structure):
+    """isal_hip_dif"""
+    _fields_ = [("type", ctypes.c_int), ("flags", ctypes.c_uint), ("app_tag", ctypes.c_ushort),
+                ("seed", ctypes.c_ushort), ("ref0", ctypes.c_void_p)]
+
+
+def _sector_t10dif(kind: str, h, sector: int, seed: int, crc, stream: int) -> None:
+    name = f"isal_hip_{kind}_sector_t10dif"
+    rc = getattr(lib(), name)(h, sector, seed & 0xFFFF, ctypes.c_void_p(addr(crc)), ctypes.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError(f"{name} failed ({rc})")
+
+
+def _dif(kind: str, what: str, h, sector: int, pi, bad, type: int, flags: int, app_tag: int, seed: int, ref0,
+         stream: int) -> None:
+    d = _Dif(type, flags, app_tag & 0xFFFF, seed & 0xFFFF, None if ref0 is None else addr(ref0))
+    name = f"isal_hip_{kind}_dif_{what}"
+    tail = (ctypes.c_void_p(addr(bad)),) if what == "verify" else ()
+    rc = getattr(lib(), name)(h, sector, ctypes.byref(d), ctypes.c_void_p(addr(pi)), *tail, ctypes.c_void_p(stream))
+    if rc != 0:
+        raise RuntimeError(f"{name} failed ({rc})")
+
 
 def addr(buf) -> int:
     """Address of a byte buffer: numpy array, torch tensor, ctypes buffer or int."""
@@ -414,6 +452,29 @@ class Batch:
                                                ctypes.c_void_p(addr(crc)), ctypes.c_void_p(stream))
         if rc != 0:
             raise RuntimeError(f"isal_hip_batch_sector_crc64 failed ({rc})")
+
+    def sector_t10dif(self, sector: int, seed: int, crc, stream: int = 0) -> None:
+        """crc16_t10dif(seed, sector bytes, n), the T10 / NVMe 16-bit guard, of
+        every sector into the DEVICE buffer crc: uint16 words laid out as
+        sector_crc()'s. One launch (isal_hip_batch_sector_t10dif)."""
+        _sector_t10dif("batch", self._h, sector, seed, crc, stream)
+
+    def dif_generate(self, sector: int, pi, type: int = DIF_TYPE1, app_tag: int = 0, seed: int = 0, ref0=None,
+                     stream: int = 0) -> None:
+        """The 8-byte T10 tuple (guard, application tag, reference tag, each
+        big-endian) of every sector into the DEVICE buffer pi (8-byte aligned,
+        8 bytes per sector in sector_crc()'s order). ref0: DEVICE uint32 per
+        shard (None: 0); DIF_TYPE1 adds the sector's index, DIF_TYPE3 does
+        not. One launch (isal_hip_batch_dif_generate)."""
+        _dif("batch", "generate", self._h, sector, pi, None, type, 0, app_tag, seed, ref0, stream)
+
+    def dif_verify(self, sector: int, pi, bad, type: int = DIF_TYPE1, flags: int = DIF_CHECK_ALL, app_tag: int = 0,
+                   seed: int = 0, ref0=None, stream: int = 0) -> None:
+        """Compares every sector with its stored tuple in pi, in the fields
+        `flags` names: the DEVICE uint32 bad[s*(k+rows) + j] becomes DIF_CLEAN,
+        or (i << 3) | kinds for the first failing sector i of the shard. A
+        fill of bad and one launch (isal_hip_batch_dif_verify)."""
+        _dif("batch", "verify", self._h, sector, pi, bad, type, flags, app_tag, seed, ref0, stream)
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -805,6 +866,29 @@ class Ragged:
                                                 ctypes.c_void_p(addr(crc)), ctypes.c_void_p(stream))
         if rc != 0:
             raise RuntimeError(f"isal_hip_ragged_sector_crc64 failed ({rc})")
+
+    def sector_t10dif(self, sector: int, seed: int, crc, stream: int = 0) -> None:
+        """crc16_t10dif(seed, sector bytes, n), the T10 / NVMe 16-bit guard, of
+        every sector into the DEVICE buffer crc: uint16 words laid out as
+        sector_crc()'s. One launch (isal_hip_ragged_sector_t10dif)."""
+        _sector_t10dif("ragged", self._h, sector, seed, crc, stream)
+
+    def dif_generate(self, sector: int, pi, type: int = DIF_TYPE1, app_tag: int = 0, seed: int = 0, ref0=None,
+                     stream: int = 0) -> None:
+        """The 8-byte T10 tuple (guard, application tag, reference tag, each
+        big-endian) of every sector into the DEVICE buffer pi (8-byte aligned,
+        8 bytes per sector in sector_crc()'s order). ref0: DEVICE uint32 per
+        shard (None: 0); DIF_TYPE1 adds the sector's index, DIF_TYPE3 does
+        not. One launch (isal_hip_ragged_dif_generate)."""
+        _dif("ragged", "generate", self._h, sector, pi, None, type, 0, app_tag, seed, ref0, stream)
+
+    def dif_verify(self, sector: int, pi, bad, type: int = DIF_TYPE1, flags: int = DIF_CHECK_ALL, app_tag: int = 0,
+                   seed: int = 0, ref0=None, stream: int = 0) -> None:
+        """Compares every sector with its stored tuple in pi, in the fields
+        `flags` names: the DEVICE uint32 bad[s*(k+rows) + j] becomes DIF_CLEAN,
+        or (i << 3) | kinds for the first failing sector i of the shard. A
+        fill of bad and one launch (isal_hip_ragged_dif_verify)."""
+        _dif("ragged", "verify", self._h, sector, pi, bad, type, flags, app_tag, seed, ref0, stream)
 
     def close(self) -> None:
         if getattr(self, "_h", None):
